@@ -2,6 +2,7 @@
 """Benchmark: all-pairs Needleman-Wunsch on MI355X, reference metric GCUPS.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|big13|c4|c5]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = the whole getMinimumPenalties job of the workload (skel:117-175,
 sub:232-364): every pair's fill + traceback + trim + SHA-512 on its rank's GPU,
@@ -12,16 +13,27 @@ scaling: the workload is fixed, its pairs are LPT-sharded over N GPUs).
 
 Default workload = C3 (BASELINE.json configs[2]), the configuration the
 north_star target is quoted on: synthetic k=64, L=50,000 ACGT, pxy=3 pgap=2,
-2,016 pairs, 5.04e12 cells.  Its answer hash and penalties are checked in-run
-against tests/golden/large/c3.json (oracle/_ref/sub, the reference's own
-program compiled from its sources, run in the build container).  big13 is
-checked against the reference's published answer (testing3/sequential.txt).
+2,016 pairs, 5.04e12 cells.
+
+A plain run does what the headline figure needs and no more: set-up, the
+warm-up steps, the K timed steps, and the result line (metric, value, unit,
+ms_per_step, ...).  --dump-outputs DIR also writes what the last timed step
+returned to its caller -- penalties.npy (P), problem_hashes.npy (P x 64 bytes)
+and answer_hash.npy (64 bytes), as float64 / float32 -- so that two builds can
+be compared output for output (the inputs are seeded: identical from run to run).
+
+--full adds everything else.  The answer hash and penalties of the warm-up
+steps and of the last timed step are checked in-run against tests/golden/large/c3.json (recorded from
+oracle/_ref/sub, the reference's own program compiled from its sources);
+big13 is checked against the reference's published answer
+(testing3/sequential.txt); a wrong answer fails the run.
 
 --gpus N without torch.distributed.run: the bench launches N rank processes
 itself (before anything touches the GPU) and fails if N exceeds the visible
 devices; under torch.distributed.run, --gpus must equal WORLD_SIZE.
 
-Also reported (rank 0):
+Also reported with --full (rank 0):
+  kernel        fill / traceback time per step from the engine's own stats.
   roofline      the fill kernel (99.5% of GPU time).  Its per-launch duration
                 is measured live (HIP events on the engine stream).  Its
                 per-launch counters -- VALU wave-instructions, GRBM_GUI_ACTIVE,
@@ -367,6 +379,19 @@ def mapped_libs():
     return sorted(libs)
 
 
+def dump_outputs(path, pen, hs, h):
+    """What the timed path handed its caller in the last timed step: every pair's
+    penalty, its 64-byte problem hash, and the chained answer hash (bytes as
+    numbers 0..255).  C4, the largest workload, is 32,640 x 64 float32 = 8 MB."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "penalties.npy"), np.asarray(pen, dtype=np.float64))
+    if hs is not None:
+        np.save(os.path.join(path, "problem_hashes.npy"), np.asarray(hs, dtype=np.uint8).astype(np.float32))
+    if h:
+        np.save(os.path.join(path, "answer_hash.npy"),
+                np.frombuffer(bytes.fromhex(h), dtype=np.uint8).astype(np.float32))
+
+
 def nwdist_auto_chunks(P, world):
     import dist as nwdist
 
@@ -384,7 +409,11 @@ def main():
                     help="go,ge: run the affine-gap variant (default for --workload c5: 3,1)")
     ap.add_argument("--kernel", default="auto",
                     help="linear fill kernel (seqalign.Engine.KERNEL): auto, nw_align_bits, nw_align_col, ...")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also: in-run answer check, kernel and roofline figures, runtime libraries, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args()
 
@@ -429,6 +458,8 @@ def main():
     name, pxy, pgap, genes, affine, expect = load_workload(args.workload)
     if args.affine is not None:
         affine = tuple(int(v) for v in args.affine.split(","))
+    if not args.full:
+        expect = None  # the answer check belongs to --full
     if affine and tuple(affine) != (0, pgap) and (expect is None or tuple(expect.get("affine", ())) != tuple(affine)):
         expect = None  # the reference's answers are for linear gaps (== affine go=0, ge=pgap only)
     elif affine and expect is not None and "affine" in expect and tuple(affine) == (0, pgap):
@@ -539,9 +570,12 @@ def main():
         launches = sum(x["fill_launches"] for x in piece_stats)
     sync()
     dt = time.perf_counter() - t0
-    checks.append(check(pen, h))  # the last timed step's answer
+    if args.steps:
+        checks.append(check(pen, h))  # the last timed step's answer
     if sharded:
         dt = comm.max(dt)  # the slowest rank's time
+    if rank == 0 and args.dump_outputs and args.steps:
+        dump_outputs(args.dump_outputs, pen, last_hs[0], h)
     if rank != 0:
         eng.close()
         if node is not None:
@@ -552,11 +586,6 @@ def main():
     ms_step = dt / max(args.steps, 1) * 1e3
     gcups = total_cells * args.steps / dt / 1e9
     st = eng.stats()
-    my_cells = workloads.cells(genes, my_ids) if sharded else total_cells
-    fill_ms = float(np.mean(fills)) if fills else float("nan")
-    launches = max(launches, 1)
-    kernel = seqalign.KERNELS.get(st["mode"], "?")
-    answer_ok = None if expect is None else all(c is True for c in checks)
     out = {
         "metric": METRIC,
         "value": round(gcups, 3),
@@ -587,6 +616,21 @@ def main():
                    "parallelism": "pair-sharded dp%d (LPT), %d all-gather(s) of 72-B records, chain streamed on rank 0%s" % (
                        world, chunks if sharded and not affine and node is None else 1,
                        "; one launch per rank, records streamed per pair (fused device finalize)" if stream else "")},
+    }
+    if not args.full:  # a plain run ends here: the headline figure and what it was measured on
+        print(json.dumps(out), flush=True)
+        eng.close()
+        if node is not None:
+            node.close()
+        if comm is not None:
+            comm.close()
+        return
+    my_cells = workloads.cells(genes, my_ids) if sharded else total_cells
+    fill_ms = float(np.mean(fills)) if fills else float("nan")
+    launches = max(launches, 1)
+    kernel = seqalign.KERNELS.get(st["mode"], "?")
+    answer_ok = None if expect is None else all(c is True for c in checks)
+    out.update({
         "answer_hash_ok": answer_ok,
         "answer_source": expect["source"] if expect else None,
         "answer_checked": None if expect is None else (
@@ -599,7 +643,7 @@ def main():
                    "window": st.get("window", 0)},
         "roofline": roofline(args.workload if not args.affine else args.workload + "_affine", kernel,
                              fill_ms / launches * 1e-3, my_cells, launches),
-    }
+    })
     if sharded:
         out["collective"] = {"backend": comm.backend,
                              "all_gathers_per_step": 1 if affine or node is not None else chunks,

@@ -66,12 +66,57 @@ def test_rank_launcher_stops_peers_on_first_failure():
     assert bench.wait_ranks(ok) == 0
 
 
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    """bench.dump_outputs: penalties as float64, hash bytes as float32 numbers 0..255."""
+    import numpy as np
+
+    import bench
+
+    pen = np.array([7, -3, 150000], dtype=np.int32)
+    hs = np.arange(3 * 64, dtype=np.uint8).reshape(3, 64)
+    h = "00ff" * 32
+    d = tmp_path / "dump"
+    bench.dump_outputs(str(d), pen, hs, h)
+    assert sorted(os.listdir(d)) == ["answer_hash.npy", "penalties.npy", "problem_hashes.npy"]
+    p = np.load(d / "penalties.npy")
+    assert p.dtype == np.float64 and p.tolist() == [7.0, -3.0, 150000.0]
+    q = np.load(d / "problem_hashes.npy")
+    assert q.dtype == np.float32 and q.shape == (3, 64) and np.array_equal(q, hs)
+    a = np.load(d / "answer_hash.npy")
+    assert a.dtype == np.float32 and a.astype(np.uint8).tobytes().hex() == h
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_published_answer(golden, tmp_path):
+    """A plain run prints the headline line only (what --full adds is absent),
+    times exactly --steps steps, and --dump-outputs holds big13's published
+    penalties and answer hash."""
+    import numpy as np
+
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "-u", BENCH, "--gpus", "1", "--workload", "big13", "--steps", "2",
+                        "--warmup", "0", "--dump-outputs", str(d)], stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, env=_env(), timeout=110)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.decode().strip().split("\n")[-1])
+    assert line["unit"] == "GCUPS" and line["higher_is_better"] is True and line["steps"] == 2
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["metric"] and line["dtype"]
+    cells = line["config"]["cells"]
+    assert abs(line["value"] - cells / (line["ms_per_step"] * 1e-3) / 1e9) <= 0.01 * line["value"]
+    for key in ("cpu_baseline", "roofline", "kernel", "answer_hash_ok", "runtime_libs"):
+        assert key not in line
+    g = golden["big13"]
+    assert np.load(d / "penalties.npy").tolist() == [float(v) for v in g["penalties"]]
+    assert np.load(d / "answer_hash.npy").astype(np.uint8).tobytes().hex() == g["hash"]
+    assert np.load(d / "problem_hashes.npy").shape == (len(g["penalties"]), 64)
+
+
 @pytest.mark.gpu
 def test_two_ranks_share_one_gpu_big13_published_hash():
     env = _env(NWK_BENCH_BACKEND="gloo", NWK_BENCH_SHARE_GPU="1", NWK_BENCH_WS_GB="110")
     r = subprocess.run([sys.executable, "-u", BENCH, "--gpus", "2", "--workload", "big13", "--steps", "1",
-                        "--warmup", "0", "--no-cpu-baseline"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       env=env, timeout=110)
+                        "--warmup", "0", "--full", "--no-cpu-baseline"], stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, env=env, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.decode().strip().split("\n")[-1])
     assert line["n_gpus"] == 2
@@ -97,8 +142,8 @@ def test_bench_nccl_all_gather_at_world_one():
     env = _env(WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                NWK_BENCH_FORCE_DIST="1", NWK_BENCH_WS_GB="110")
     r = subprocess.run([sys.executable, "-u", BENCH, "--gpus", "1", "--workload", "big13", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       env=env, timeout=110)
+                        "--warmup", "1", "--full", "--no-cpu-baseline"], stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, env=env, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.decode().strip().split("\n")[-1])
     assert line["answer_hash_ok"] is True
@@ -129,8 +174,8 @@ def test_two_ranks_streamed_records_big13_published_hash(node):
                NWK_BENCH_STREAM="1", NWK_BENCH_CHUNKS="4", NWK_NODE_RECORDS="0" if node == "0" else "1",
                NWK_BENCH_RECORDS="1" if node == "records" else "0")
     r = subprocess.run([sys.executable, "-u", BENCH, "--gpus", "2", "--workload", "big13",
-                        "--steps", "1", "--warmup", "0", "--no-cpu-baseline"], stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, env=env, timeout=110)
+                        "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.decode().strip().split("\n")[-1])
     assert line["n_gpus"] == 2 and line["answer_hash_ok"] is True

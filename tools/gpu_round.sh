@@ -33,7 +33,7 @@ for s in $STEPS; do
       run pytest_gpu 1000 python -u -m pytest tests/ -x -v -m gpu --timeout 150 --timeout-method thread ${PYTEST_K:+-k "$PYTEST_K"}
       ;;
     bench)
-      run bench_$WL 600 python3 bench.py --workload "$WL" --steps "${BSTEPS:-5}" --warmup 1 $BENCH_ARGS
+      run bench_$WL 600 python3 bench.py --workload "$WL" --steps "${BSTEPS:-5}" --warmup 1 --full $BENCH_ARGS
       ;;
     prof)
       run prof_$WL 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$WL" -o run --output-format csv -- python3 bench.py --workload "$WL" --steps 2 --warmup 1 --no-cpu-baseline $BENCH_ARGS
