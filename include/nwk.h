@@ -66,10 +66,9 @@ typedef struct nwk_opts {
   int32_t linear_space;      /* linear-space traceback: 0 = only for pairs whose matrix exceeds
                                 the HBM budget, -1 = never, G > 0 = every pair, G bands per recompute group */
   int32_t kernel;            /* linear fill kernel: 0 auto (where admissible -- pxy >= 0, pgap 1 or 2, <= 4
-                                symbols -- nw_align_col, unless the job is more than 3 rounds of wave slots of
-                                2048-row bands and has pairs longer than 16k, then nw_align_bits as band tasks or,
-                                for jobs of many pairs per wave slot, one rolling strip per pair, nw_align_strip;
-                                elsewhere the integer kernels), 1 nw_align, 2 nw_align_pk,
+                                symbols -- nw_align_col for jobs of every size, one band per task (NWK_COL_PAIR=1:
+                                two bands per task, measured slower); elsewhere the integer kernels), 1 nw_align,
+                                2 nw_align_pk,
                                 3 nw_align_pk2, 4 nw_align_bits band tasks, 5 nw_align_strip wherever admissible
                                 (n / 64 in [63, 200] for pgap 2, [63, 500] for pgap 1), 6 nw_align_col (bit-parallel
                                 columns, nw_align_bits' domain; a kernel where it is not exact -- W > 4, mixed-sign K,
@@ -104,6 +103,7 @@ typedef struct nwk_stats {
   int32_t window;            /* storage window W in columns of the call's first pairs (0 = full storage) */
   int32_t guard_checked;     /* pairs whose walked path's cost was checked against the fill's own dp[m][n] */
   int32_t guard_reruns;      /* pairs re-run because their walked path's cost differed from it (skel:274) */
+  int32_t col_paired_tasks;  /* nw_align_col: tasks of the call that filled two bands (paired tasks) */
 } nwk_stats;
 
 /* Defaults for nwk_opts (device 0, auto everything). */

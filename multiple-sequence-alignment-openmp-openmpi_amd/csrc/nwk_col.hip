@@ -73,6 +73,27 @@ __device__ __forceinline__ void col_hop(u64& c, unsigned& acc, u64 inj) {
   c = ((u64)hi << 32) | lo;
 }
 
+// The hop of a paired task (two words: band b in word A, band b + 1 in word B,
+// 64 steps behind, as lanes 64 .. 127 of one virtual wave): A's lane-63 carry
+// out of the previous step is B's lane-0 carry in, so one SCC chain runs
+// through both words and B's bit 63 enters acc (B's last row).  6 SALU for two
+// words; the boundary between A and B never touches memory.
+template <int QQ>
+__device__ __forceinline__ void col_hop2(u64& ca, u64& cb, unsigned& acc, unsigned inj) {
+  unsigned la = (unsigned)ca, ha = (unsigned)(ca >> 32), lb = (unsigned)cb, hb = (unsigned)(cb >> 32);
+  asm("s_bitcmp1_b32 %[inj], %[pos]\n\t"
+      "s_addc_u32 %[la], %[la], %[la]\n\t"
+      "s_addc_u32 %[ha], %[ha], %[ha]\n\t"
+      "s_addc_u32 %[lb], %[lb], %[lb]\n\t"
+      "s_addc_u32 %[hb], %[hb], %[hb]\n\t"
+      "s_addc_u32 %[acc], %[acc], %[acc]"
+      : [la] "+s"(la), [ha] "+s"(ha), [lb] "+s"(lb), [hb] "+s"(hb), [acc] "+s"(acc)
+      : [inj] "s"(inj), [pos] "i"(QQ)
+      : "scc");
+  ca = ((u64)ha << 32) | la;
+  cb = ((u64)hb << 32) | lb;
+}
+
 // G_K's middle terms OR_{d = D .. I-1} (~l_d & T_{K+d})
 template <int NP, int K, int D, int I>
 __device__ __forceinline__ unsigned col_mid(unsigned G, const unsigned (&l)[NP], const unsigned (&T)[NP]) {
@@ -110,86 +131,102 @@ __device__ __forceinline__ void col_level(unsigned match, unsigned P, const unsi
   }
 }
 
-template <int NP, int SR, int K>
-__device__ __forceinline__ void col_levels(unsigned match, unsigned P, const unsigned (&l)[NP], unsigned (&T)[NP],
-                                           u64 (&c)[NP]) {
-  col_level<NP, SR, K>(match, P, l, T, c[K]);
-  if constexpr (K > 0) col_levels<NP, SR, K - 1>(match, P, l, T, c);
+// (two words: level K of both words, then level K - 1: the words are independent, so
+// one word's v_addc and its scalar neighbours fill the other's dependent slots)
+template <int NW, int NP, int SR, int K>
+__device__ __forceinline__ void col_levels(const unsigned (&match)[NW], const unsigned (&l)[NW][NP],
+                                           unsigned (&T)[NW][NP], u64 (&c)[NW][NP]) {
+#pragma unroll
+  for (int w = 0; w < NW; ++w) col_level<NP, SR, K>(match[w], ~l[w][0], l[w], T[w], c[w][K]);
+  if constexpr (K > 0) col_levels<NW, NP, SR, K - 1>(match, l, T, c);
 }
 
-template <int NP, int QQ, int K = 0>
-__device__ __forceinline__ void col_hops(u64 (&c)[NP], unsigned (&acc)[NP], const u64 (&inj)[NP]) {
-  col_hop<QQ>(c[K], acc[K], inj[K]);
-  if constexpr (K + 1 < NP) col_hops<NP, QQ, K + 1>(c, acc, inj);
+template <int NW, int NP, int QQ, int K = 0>
+__device__ __forceinline__ void col_hops(u64 (&c)[NW][NP], unsigned (&acc)[NP], const u64 (&inj)[NP]) {
+  if constexpr (NW == 1) col_hop<QQ>(c[0][K], acc[K], inj[K]);
+  else col_hop2<QQ>(c[0][K], c[1][K], acc[K], (unsigned)inj[K]);
+  if constexpr (K + 1 < NP) col_hops<NW, NP, QQ, K + 1>(c, acc, inj);
 }
 
-// Eight steps s0 .. s0+7 (s0 % 8 == 0) of one band.
+// Eight steps s0 .. s0+7 (s0 % 8 == 0) of one band (NW = 1), or of two
+// consecutive bands in words A and B (NW = 2: word w is lanes 64 w .. 64 w + 63
+// of a 128-lane virtual wave, so B works 64 steps behind A; x0 .. l, c, st and
+// sto are per word).
 //   x0, x1   code bit planes of this lane's 32 rows
-//   w0, w1   y window of this 32-step half (bit 31 - q = code of column s_half + q - lane)
+//   w0, w1   y window of this 32-step half (bit 31 - q = code of column s_half + q - lane - 64 w)
 //   l        v planes of this lane's previous column
 //   c        per level: the carries out of the previous step (64-lane masks)
-//   acc      shift registers of lane 63's carries out (the band's last row)
+//   acc      shift registers of the last word's lane-63 carries out (the last row of the task's last band)
 //   inj      the band above's last row for lane 0's columns of this half (bit q = column s_half + q)
-//   pub      CAP: acc after step s_half + 30's carries (columns s_half - 94 .. s_half - 63)
-//   MASK     steps of the first super-block: columns < 0 keep v = 0 (the left border)
-//   END      steps that may hold column capc = n - 1: lane t = s - capc holds it;
+//   pub      CAP: acc after step s_half + 30's carries (columns s_half - 94 - 64 (NW - 1) .. + 31)
+//   MASK     bit w: word w may hold columns < 0 (its first 64 (w + 1) steps), which keep v = 0 (the left border)
+//   END      steps that may hold column capc = n - 1: virtual lane t = s - capc holds it;
 //            the scalar unit reads its vertical differences (v_readlane) and adds
 //            those of its rows < m (nvr0 - 32 t of them) to cnt (the fill-vs-walk
 //            guard's end value, FillArgs::endv).  All scalar: no VGPR lives
 //            across the loop for it (a per-lane mask and counter did, and the
 //            96-VGPR instantiation spilled ~270 registers: C3 145 -> 172 ms)
-template <int NP, int SR, bool MASK, bool CAP, int BLK, bool END>
-__device__ __forceinline__ void col_block(int s0, int lane, unsigned x0, unsigned x1, unsigned w0, unsigned w1,
-                                          unsigned (&l)[NP], u64 (&c)[NP], unsigned (&acc)[NP],
-                                          const u64 (&inj)[NP], unsigned (&pub)[NP], unsigned* st, bool sto,
+template <int NW, int NP, int SR, int MASK, bool CAP, int BLK, bool END>
+__device__ __forceinline__ void col_block(int s0, int lane, const unsigned (&x0)[NW], const unsigned (&x1)[NW],
+                                          const unsigned (&w0)[NW], const unsigned (&w1)[NW], unsigned (&l)[NW][NP],
+                                          u64 (&c)[NW][NP], unsigned (&acc)[NP], const u64 (&inj)[NP],
+                                          unsigned (&pub)[NP], unsigned* const (&st)[NW], const bool (&sto)[NW],
                                           int capc, int nvr0, int& cnt) {
-  unsigned dw[8], uw[8];
-  auto step = [&](auto qc) {
+  unsigned dw[NW][8], uw[NW][8];
+  auto step = [&](auto qc) __attribute__((always_inline)) {
     constexpr int q = decltype(qc)::value;
     constexpr int qq = 8 * BLK + q;  // step s0 + q within its 32-step half
     const int s = s0 + q;
-    const unsigned Y0 = (unsigned)((int)(w0 << qq) >> 31);  // code bits of column s - lane, as 0 / ~0
-    const unsigned Y1 = (unsigned)((int)(w1 << qq) >> 31);
-    const unsigned match = BOP3(x0 ^ Y0, x1, Y1, ~(kA | (kB ^ kC)));  // ~((x0^Y0) | (x1^Y1))
-    col_hops<NP, qq>(c, acc, inj);
+    col_hops<NW, NP, qq>(c, acc, inj);
     if constexpr (CAP && q == 7) {
 #pragma unroll
       for (int k = 0; k < NP; ++k) pub[k] = acc[k];
     }
-    unsigned T[NP], D[NP], Vn[NP];
-    const unsigned P = ~l[0];
-    col_levels<NP, SR, NP - 1>(match, P, l, T, c);
+    unsigned mt[NW], Tw[NW][NP];
 #pragma unroll
-    for (int k = 0; k < NP; ++k) D[k] = k < SR ? ~0u : BOP3(match, T[k], l[k], kA | kB | kC);
-    bits_diffs<NP, SR>(T, D, Vn);  // v = D - U, U = T
-    if constexpr (MASK) {
-      const bool live = s >= lane;  // column s - lane >= 0
-#pragma unroll
-      for (int k = 0; k < NP; ++k) Vn[k] = live ? Vn[k] : 0u;
+    for (int w = 0; w < NW; ++w) {
+      const unsigned Y0 = (unsigned)((int)(w0[w] << qq) >> 31);  // code bits of this lane's column, as 0 / ~0
+      const unsigned Y1 = (unsigned)((int)(w1[w] << qq) >> 31);
+      mt[w] = BOP3(x0[w] ^ Y0, x1[w], Y1, ~(kA | (kB ^ kC)));  // ~((x0^Y0) | (x1^Y1))
     }
+    col_levels<NW, NP, SR, NP - 1>(mt, l, Tw, c);
 #pragma unroll
-    for (int k = 0; k < NP; ++k) l[k] = Vn[k];
-    if constexpr (END) {
-      const int t = s - capc;  // (uniform) the lane at column capc
-      if ((unsigned)t < 64u) {
-        const int nv = nvr0 - 32 * t;
-        const unsigned mk = nv >= 32 ? ~0u : (nv <= 0 ? 0u : (1u << nv) - 1u);
+    for (int w = 0; w < NW; ++w) {
+      const unsigned match = mt[w];
+      unsigned (&T)[NP] = Tw[w];
+      unsigned D[NP], Vn[NP];
 #pragma unroll
-        for (int k = 0; k < NP; ++k) cnt += __builtin_popcount((unsigned)__builtin_amdgcn_readlane((int)Vn[k], t) & mk);
+      for (int k = 0; k < NP; ++k) D[k] = k < SR ? ~0u : BOP3(match, T[k], l[w][k], kA | kB | kC);
+      bits_diffs<NP, SR>(T, D, Vn);  // v = D - U, U = T
+      if ((MASK >> w) & 1) {
+        const bool live = s >= lane + 64 * w;  // the lane's column >= 0
+#pragma unroll
+        for (int k = 0; k < NP; ++k) Vn[k] = live ? Vn[k] : 0u;
       }
-    }
-    if constexpr (SR < 0) dw[q] = match;
-    else if constexpr (SR >= NP) dw[q] = ~0u;
-    else dw[q] = BOP3(match, D[SR], D[SR], kA | ~kB);  // match | ~D_SR
-    uw[q] = Vn[0];  // stored raw: UP is v == 0 (bit clear)
-    if constexpr ((q & 3) == 3) {
-      typedef unsigned u4 __attribute__((ext_vector_type(4)));
-      constexpr int h = q >> 2;
-      if (sto) {
-        __builtin_nontemporal_store(u4{dw[4 * h], dw[4 * h + 1], dw[4 * h + 2], dw[4 * h + 3]},
-                                    reinterpret_cast<u4*>(st + 256 * h));
-        __builtin_nontemporal_store(u4{uw[4 * h], uw[4 * h + 1], uw[4 * h + 2], uw[4 * h + 3]},
-                                    reinterpret_cast<u4*>(st + 512 + 256 * h));
+#pragma unroll
+      for (int k = 0; k < NP; ++k) l[w][k] = Vn[k];
+      if constexpr (END) {
+        const int t = s - capc - 64 * w;  // (uniform) the lane of this word at column capc
+        if ((unsigned)t < 64u) {
+          const int nv = nvr0 - 2048 * w - 32 * t;
+          const unsigned mk = nv >= 32 ? ~0u : (nv <= 0 ? 0u : (1u << nv) - 1u);
+#pragma unroll
+          for (int k = 0; k < NP; ++k) cnt += __builtin_popcount((unsigned)__builtin_amdgcn_readlane((int)Vn[k], t) & mk);
+        }
+      }
+      if constexpr (SR < 0) dw[w][q] = match;
+      else if constexpr (SR >= NP) dw[w][q] = ~0u;
+      else dw[w][q] = BOP3(match, D[SR], D[SR], kA | ~kB);  // match | ~D_SR
+      uw[w][q] = Vn[0];  // stored raw: UP is v == 0 (bit clear)
+      if constexpr ((q & 3) == 3) {
+        typedef unsigned u4 __attribute__((ext_vector_type(4)));
+        constexpr int h = q >> 2;
+        if (sto[w]) {
+          __builtin_nontemporal_store(u4{dw[w][4 * h], dw[w][4 * h + 1], dw[w][4 * h + 2], dw[w][4 * h + 3]},
+                                      reinterpret_cast<u4*>(st[w] + 256 * h));
+          __builtin_nontemporal_store(u4{uw[w][4 * h], uw[w][4 * h + 1], uw[w][4 * h + 2], uw[w][4 * h + 3]},
+                                      reinterpret_cast<u4*>(st[w] + 512 + 256 * h));
+        }
       }
     }
   };
@@ -984,8 +1021,15 @@ __device__ __forceinline__ void trace_col(const FillArgs& a, const PairDesc& pd,
 #define NWK_COL_WPE_HI 5
 #endif
 
+// The paired instantiation (two-word tasks next to one-word ones) needs ~40
+// VGPRs more than the one-word form and runs at NWK_COL_WPE_PAIR waves per SIMD.
+#ifndef NWK_COL_WPE_PAIR
+#define NWK_COL_WPE_PAIR 4
+#endif
+
 // FUSE: the instantiation with the fused finalize (FillArgs::fuse_fin)
-template <int NP, int SR, bool FUSE, int WPE>
+// PAIR: the instantiation that also holds the two-word fill (tasks with kColTaskPair)
+template <int NP, int SR, bool FUSE, int WPE, bool PAIR = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void nw_align_col(FillArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char obuf_all[4][kTraceRing];
   __shared__ __attribute__((aligned(16))) unsigned pf_all[4][512];  // trace_col's tile ahead (LDS-DMA)
@@ -1013,7 +1057,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     const u64 t_task = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
     const int2 task = a.tasks[tk];
     const PairDesc pd = a.pairs[task.x];
-    const int band = task.y;
+    // a task fills one band, or (PAIR, kColTaskPair set) bands band and band + 1 as one paired task
+    const int band = task.y & (kColTaskPair - 1);
+    const int nwd = PAIR && (task.y & kColTaskPair) ? 2 : 1;
     const int R0 = band * kBR;
     // the longest spans of a span-bound batch issue ahead of the other fill waves
     // (band_prio: a pair's bands run as a pipeline at the pace of its slowest
@@ -1024,50 +1070,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     else if (prio == 2) __builtin_amdgcn_s_setprio(2);
     else if (prio == 1) __builtin_amdgcn_s_setprio(1);
     else __builtin_amdgcn_s_setprio(0);
-    // code bit planes of rows R0 + 32 lane + b (rows past m: code 0, never traced)
-    unsigned x0 = 0, x1 = 0;
-    {
-      const int base = R0 + 32 * lane;
-      const int nv = pd.m - base;
-      const uint8_t* xc = a.codes + pd.x_off + base;
-#pragma unroll
-      for (int b = 0; b < 32; ++b) {
-        const unsigned cd = b < nv ? (unsigned)xc[b] : 0u;
-        x0 |= (cd & 1u) << b;
-        x1 |= ((cd >> 1) & 1u) << b;
-      }
-    }
-    unsigned l[NP], acc[NP], pub[NP];
-    u64 c[NP], inj[NP];
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-      l[k] = acc[k] = pub[k] = 0u;
-      c[k] = inj[k] = 0ull;
-    }
-    const bool from_above = band > 0;
-    const bool to_below = band + 1 < pd.nbands;
     const int nw = (pd.n + 31) >> 5;  // 32-column words of a row
     const int nsb = pd.sblocks;
-    const u64* gin = reinterpret_cast<const u64*>(a.bnd) + pd.bnd_off + (int64_t)(from_above ? band - 1 : 0) * nw * NP;
-    u64* gout = a.bnd + pd.bnd_off + (int64_t)band * nw * NP;
-    const int nblk = pd.bits_nblk, blo = bits_blk_lo(band, pd.m, pd.n, pd.bits_w);
-    unsigned* mb = a.mat + pd.mat_off + (int64_t)band * nblk * 1024 + lane * 4;
+    const int nblk = pd.bits_nblk;
     // windowed storage, per lane and 8-step block: its words hold rows R0 + 32 lane ..
     // + 31 at columns s0 - lane .. + 7, so dev = c m - i n spans [hi - 7 m - 31 n, hi]
     // with hi = (s0 - lane + 7) m - (R0 + 32 lane) n = s0 m + hi0 (bits_lane_stored)
     const bool win = pd.bits_w > 0;
     const int64_t lim = (int64_t)pd.bits_w * pd.m, hlim = lim + 7ll * pd.m + 31ll * pd.n;
-    const int64_t hi0 = (int64_t)(7 - lane) * pd.m - (int64_t)(R0 + 32 * lane) * pd.n;
     // y windows: lane t's window for the half starting at step s_h is position s_h - t
     const unsigned* ywp = a.yw + 2 * (pd.e_off - (int64_t)lane);
-    unsigned wc0 = ywp[0], wc1 = ywp[1];
     // granule k of a 32-column word is polled by lane k; every lane loads one
     // (lanes >= NP a copy) so no branch depends on the lane: a lane-dependent
     // branch here would make the compiler treat the carries as per-lane values
     const bool gl = lane < NP;
     const int gk = lane & (NP - 1);
-    u64 g = 0;
-    if (from_above) g = __hip_atomic_load((gu64*)(gin + gk), BITS_RLX);
+    const bool from_above = band > 0;
+    const u64* gin = reinterpret_cast<const u64*>(a.bnd) + pd.bnd_off + (int64_t)(from_above ? band - 1 : 0) * nw * NP;
     bool ok = true;
     u64 cyc_wait = 0, cyc_wait0 = 0, n_wait = 0;  // (verbose >= 2 timeline)
     // fill-vs-walk guard: G(m, n) = -sum of v down column n (G-space borders are
@@ -1081,77 +1100,171 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     int cnt = 0;                  // (uniform)
     const int nvr0 = pd.m - R0;   // rows < m from lane 0's first row on
 
-    auto half = [&](int h, auto mask_t, auto end_t) {
-      constexpr bool MASK = decltype(mask_t)::value;
-      constexpr bool END = decltype(end_t)::value;
-      const unsigned* wp = ywp + 64 * (h + 1);
-      const unsigned nx0 = wp[0], nx1 = wp[1];  // the next half's window
-      if (from_above) {
-        if (h < nw) {
-          if (!wall(!gl || (unsigned)(g >> 32) == a.epoch)) {
-            const u64 tw = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
-            g = bits_wait(gin + (int64_t)h * NP + gk, gl, a.epoch, g, a.err);
-            if (a.stamps) {
-              const u64 d = __builtin_amdgcn_s_memtime() - tw;
-              cyc_wait += d;
-              if (h == 0) cyc_wait0 = d;
-              ++n_wait;
-            }
-            // (a failed wait ends the task after this half, which publishes nothing; the
-            // error word fails the call.  No early return: it would leave the carries
-            // undefined on one path, and the compiler then moves them out of SGPRs)
-            if (!wall(!gl || (unsigned)(g >> 32) == a.epoch)) ok = false;
-          }
-          const unsigned dat = (unsigned)g;
+    // The fill of NW words: NW = 1 one band; NW = 2 bands band (word A) and
+    // band + 1 (word B, the same lanes 64 steps behind: B's step s is the step
+    // s - 64 of an unpaired task of band + 1, and everything it stores has that
+    // task's layout).  The two forms share no variable that holds a carry.
+    auto fill = [&](auto nw_t) __attribute__((always_inline)) {
+      constexpr int NW = decltype(nw_t)::value;
+      constexpr int LAG = 2 * (NW - 1);  // halves the last word trails word A by
+      // code bit planes of rows R0 + 2048 w + 32 lane + b (rows past m: code 0, never traced)
+      unsigned x0[NW], x1[NW];
 #pragma unroll
-          for (int k = 0; k < NP; ++k) inj[k] = (u64)(unsigned)__builtin_amdgcn_readlane((int)dat, k);
-          if (h + 1 < nw) g = __hip_atomic_load((gu64*)(gin + (int64_t)(h + 1) * NP + gk), BITS_RLX);
-        } else {
+      for (int w = 0; w < NW; ++w) {
+        const int base = R0 + kBR * w + 32 * lane;
+        const int nv = pd.m - base;
+        const uint8_t* xc = a.codes + pd.x_off + base;
+        x0[w] = x1[w] = 0;
 #pragma unroll
-          for (int k = 0; k < NP; ++k) inj[k] = 0ull;
+        for (int b = 0; b < 32; ++b) {
+          const unsigned cd = b < nv ? (unsigned)xc[b] : 0u;
+          x0[w] |= (cd & 1u) << b;
+          x1[w] |= ((cd >> 1) & 1u) << b;
         }
       }
-      auto blk = [&](auto bc) {
-        constexpr int B = decltype(bc)::value;
-        const int s0 = 32 * h + 8 * B;
-        const int rel = (s0 >> 3) - blo;
-        // stored: the block is among the band's stored steps and (windowed) this
-        // lane's words of it hold a cell within bits_w columns of the diagonal
-        const bool sto = (unsigned)rel < (unsigned)nblk && (!win || bits_lane_stored(hi0 + (int64_t)s0 * pd.m, lim, hlim));
-        unsigned* st = mb + (int64_t)rel * 1024;
-        col_block<NP, SR, MASK, B == 3, B, END>(s0, lane, x0, x1, wc0, wc1, l, c, acc, inj, pub, st, sto, capx, nvr0,
-                                                cnt);
-      };
-      blk(std::integral_constant<int, 0>{});
-      blk(std::integral_constant<int, 1>{});
-      blk(std::integral_constant<int, 2>{});
-      blk(std::integral_constant<int, 3>{});
-      // publish the band's last row, columns 32 (h - 2) .. + 31 (lane 63's carries of steps 32 h - 1 .. 32 h + 30,
-      // MSB first in pub)
-      if (to_below && ok && h >= 2 && h - 2 < nw) {
-        unsigned v = 0;
+      unsigned l[NW][NP], acc[NP], pub[NP];
+      u64 c[NW][NP], inj[NP];
 #pragma unroll
-        for (int k = 0; k < NP; ++k) v = gk == k ? __builtin_bitreverse32(pub[k]) : v;
-        // (every lane stores: lanes >= NP repeat lane gk's granule, so no branch depends on the lane)
-        __hip_atomic_store((gu64*)(gout + (int64_t)(h - 2) * NP + gk), ((u64)a.epoch << 32) | v, BITS_RLX);
+      for (int k = 0; k < NP; ++k) {
+        acc[k] = pub[k] = 0u;
+        inj[k] = 0ull;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+          l[w][k] = 0u;
+          c[w][k] = 0ull;
+        }
       }
-      wc0 = nx0;
-      wc1 = nx1;
+      const int bl = band + NW - 1;  // the band whose last row leaves the task
+      const bool to_below = bl + 1 < pd.nbands;
+      u64* gout = a.bnd + pd.bnd_off + (int64_t)bl * nw * NP;
+      int blo[NW];
+      unsigned* mb[NW];
+      int64_t hi0[NW];
+      unsigned wc0[NW], wc1[NW];
+#pragma unroll
+      for (int w = 0; w < NW; ++w) {
+        blo[w] = bits_blk_lo(band + w, pd.m, pd.n, pd.bits_w);
+        mb[w] = a.mat + pd.mat_off + (int64_t)(band + w) * nblk * 1024 + lane * 4;
+        hi0[w] = (int64_t)(7 - lane) * pd.m - (int64_t)(R0 + kBR * w + 32 * lane) * pd.n;
+        wc0[w] = ywp[-128 * w];  // (word B: position -64 - lane, inside the front padding)
+        wc1[w] = ywp[-128 * w + 1];
+      }
+      u64 g = 0;
+      if (from_above) g = __hip_atomic_load((gu64*)(gin + gk), BITS_RLX);
+
+      auto half = [&](int h, auto mask_t, auto end_t) __attribute__((always_inline)) {
+        constexpr int MASK = decltype(mask_t)::value;
+        constexpr bool END = decltype(end_t)::value;
+        unsigned nx0[NW], nx1[NW];  // the next half's windows (word B's: A's of two halves earlier)
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+          const unsigned* wp = ywp + 64 * (h + 1 - 2 * w);
+          nx0[w] = wp[0];
+          nx1[w] = wp[1];
+        }
+        if (from_above) {
+          if (h < nw) {
+            if (!wall(!gl || (unsigned)(g >> 32) == a.epoch)) {
+              const u64 tw = a.stamps ? __builtin_amdgcn_s_memtime() : 0;
+              g = bits_wait(gin + (int64_t)h * NP + gk, gl, a.epoch, g, a.err);
+              if (a.stamps) {
+                const u64 d = __builtin_amdgcn_s_memtime() - tw;
+                cyc_wait += d;
+                if (h == 0) cyc_wait0 = d;
+                ++n_wait;
+              }
+              // (a failed wait ends the task after this half, which publishes nothing; the
+              // error word fails the call.  No early return: it would leave the carries
+              // undefined on one path, and the compiler then moves them out of SGPRs)
+              if (!wall(!gl || (unsigned)(g >> 32) == a.epoch)) ok = false;
+            }
+            const unsigned dat = (unsigned)g;
+#pragma unroll
+            for (int k = 0; k < NP; ++k) inj[k] = (u64)(unsigned)__builtin_amdgcn_readlane((int)dat, k);
+            if (h + 1 < nw) g = __hip_atomic_load((gu64*)(gin + (int64_t)(h + 1) * NP + gk), BITS_RLX);
+          } else {
+#pragma unroll
+            for (int k = 0; k < NP; ++k) inj[k] = 0ull;
+          }
+        }
+        auto blk = [&](auto bc) __attribute__((always_inline)) {
+          constexpr int B = decltype(bc)::value;
+          const int s0 = 32 * h + 8 * B;
+          // stored: the block is among the band's stored steps and (windowed) this
+          // lane's words of it hold a cell within bits_w columns of the diagonal
+          // (word B: its band's step is s0 - 64; negative steps are never stored)
+          bool sto[NW];
+          unsigned* st[NW];
+#pragma unroll
+          for (int w = 0; w < NW; ++w) {
+            const int sw = s0 - 64 * w;
+            const int rel = (sw >> 3) - blo[w];
+            sto[w] = (unsigned)rel < (unsigned)nblk && (!win || bits_lane_stored(hi0[w] + (int64_t)sw * pd.m, lim, hlim));
+            st[w] = mb[w] + (int64_t)rel * 1024;
+          }
+          col_block<NW, NP, SR, MASK, B == 3, B, END>(s0, lane, x0, x1, wc0, wc1, l, c, acc, inj, pub, st, sto, capx,
+                                                      nvr0, cnt);
+        };
+        blk(std::integral_constant<int, 0>{});
+        blk(std::integral_constant<int, 1>{});
+        blk(std::integral_constant<int, 2>{});
+        blk(std::integral_constant<int, 3>{});
+        // publish the task's last row, columns 32 (h - 2 - LAG) .. + 31 (the last word's lane-63 carries of steps
+        // 32 h - 1 .. 32 h + 30, MSB first in pub)
+        if (to_below && ok && h >= 2 + LAG && h - 2 - LAG < nw) {
+          unsigned v = 0;
+#pragma unroll
+          for (int k = 0; k < NP; ++k) v = gk == k ? __builtin_bitreverse32(pub[k]) : v;
+          // (every lane stores: lanes >= NP repeat lane gk's granule, so no branch depends on the lane)
+          __hip_atomic_store((gu64*)(gout + (int64_t)(h - 2 - LAG) * NP + gk), ((u64)a.epoch << 32) | v, BITS_RLX);
+        }
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+          wc0[w] = nx0[w];
+          wc1[w] = nx1[w];
+        }
+      };
+      using I0 = std::integral_constant<int, 0>;
+      if constexpr (NW == 1) {
+        // the first super-block (columns < 0 masked) peeled off the loop; the last
+        // ones (column n - 1) take the guard's end value
+        // (always the END form: an if / else around the peeled halves makes the
+        // compiler treat the SGPR carries as divergent; capx = -1000 matches nothing)
+        using I1 = std::integral_constant<int, 1>;
+        half(0, I1{}, std::true_type{});
+        half(1, I1{}, std::true_type{});
+        // (the loops do not end on !ok: an exit to the task's end between them makes the
+        // compiler structurize them with the carries undefined on one path, and moves the
+        // carries out of SGPRs; a failed wait sets the error word, every later wait then
+        // returns at once, and the task runs out publishing nothing)
+        int sb = 1;
+        for (; sb < sbe; ++sb) {
+          half(2 * sb, I0{}, std::false_type{});
+          half(2 * sb + 1, I0{}, std::false_type{});
+        }
+        for (; sb < nsb; ++sb) {
+          half(2 * sb, I0{}, std::true_type{});
+          half(2 * sb + 1, I0{}, std::true_type{});
+        }
+      } else {
+        // two words: a loop trip is one 32-step half (64 word-steps, the code
+        // size of the one-word loop's two).  Word B's columns are < 0 during the
+        // first four halves, and its column n - 1 passes 64 steps after A's, so
+        // the task runs one super-block longer.
+        using I3 = std::integral_constant<int, 3>;
+        // (no exit on !ok, as above)
+        int h = 0;
+        for (; h < 4; ++h) half(h, I3{}, std::true_type{});
+        const int he = 2 * (sbe > 2 ? sbe : 2), hn = 2 * (nsb + 1);
+        for (; h < he; ++h) half(h, I0{}, std::false_type{});
+        for (; h < hn; ++h) half(h, I0{}, std::true_type{});
+      }
     };
-    // the first super-block (columns < 0 masked) peeled off the loop; the last
-    // ones (column n - 1) take the guard's end value
-    // (always the END form: an if / else around the peeled halves makes the
-    // compiler treat the SGPR carries as divergent; capx = -1000 matches nothing)
-    half(0, std::true_type{}, std::true_type{});
-    half(1, std::true_type{}, std::true_type{});
-    int sb = 1;
-    for (; sb < sbe && ok; ++sb) {
-      half(2 * sb, std::false_type{}, std::false_type{});
-      half(2 * sb + 1, std::false_type{}, std::false_type{});
-    }
-    for (; sb < nsb && ok; ++sb) {
-      half(2 * sb, std::false_type{}, std::true_type{});
-      half(2 * sb + 1, std::false_type{}, std::true_type{});
+    if constexpr (PAIR) {
+      if (nwd == 2) fill(std::integral_constant<int, 2>{});
+      else fill(std::integral_constant<int, 1>{});
+    } else {
+      fill(std::integral_constant<int, 1>{});
     }
     BITS_PROG(0x30000000u);
     if (!ok) return;
@@ -1171,9 +1284,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     unsigned prev = 0;
-    if (lane == 0) prev = __hip_atomic_fetch_add((gu32*)(a.done + pd.slot), 1u, BITS_RLX);
+    if (lane == 0) prev = __hip_atomic_fetch_add((gu32*)(a.done + pd.slot), (unsigned)nwd, BITS_RLX);
     prev = __builtin_amdgcn_readfirstlane(prev);
-    if (prev + 1u == (unsigned)pd.nbands) {  // the pair's last band: every band has released
+    if (prev + (unsigned)nwd == (unsigned)pd.nbands) {  // the pair's last band: every band has released
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       BITS_PROG(0x40000000u);
@@ -1201,36 +1314,42 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
       __builtin_amdgcn_s_setprio(0);
       if (a.stamps && lane == 0) a.stamps[8 * pd.slot + 1] = __builtin_amdgcn_s_memrealtime();
       BITS_PROG(0x56000000u);
-    } else if (pd.spec_every > 0 && band + 1 < pd.nbands) {  // segmented: this band's speculative segment
+    } else if (pd.spec_every > 0) {  // segmented: the speculative segment of each band filled (but the pair's last)
       int tlen;
       int2 tend;
       bool tout;
       __builtin_amdgcn_s_setprio(3);
-      if (pd.bits_w > 0) trace_col<true, true>(a, pd, obuf_all[wid], pf_all[wid], lane, band, tlen, tend, tout);
-      else trace_col<true, false>(a, pd, obuf_all[wid], pf_all[wid], lane, band, tlen, tend, tout);
+      for (int sb = band; sb < band + nwd && sb + 1 < pd.nbands; ++sb) {
+        if (pd.bits_w > 0) trace_col<true, true>(a, pd, obuf_all[wid], pf_all[wid], lane, sb, tlen, tend, tout);
+        else trace_col<true, false>(a, pd, obuf_all[wid], pf_all[wid], lane, sb, tlen, tend, tout);
+      }
       __builtin_amdgcn_s_setprio(0);
     }
   }
 }
 
 template <int NP, int SR>
-hipError_t col_launch(const FillArgs& a, int grid, bool hi, hipStream_t s) {
+hipError_t col_launch(const FillArgs& a, int grid, bool hi, bool pair, hipStream_t s) {
 #ifdef NWK_COL_NOFUSE
   if (a.fuse_fin) return hipErrorInvalidValue;
 #else
-  if (a.fuse_fin) hipLaunchKernelGGL((nw_align_col<NP, SR, true, NWK_COL_WPE>), dim3(grid), dim3(256), 0, s, a);
-  else
+  if (a.fuse_fin) {
+    if (pair) return hipErrorInvalidValue;  // (no paired fused instantiation)
+    hipLaunchKernelGGL((nw_align_col<NP, SR, true, NWK_COL_WPE>), dim3(grid), dim3(256), 0, s, a);
+  } else
 #endif
-  if (hi) hipLaunchKernelGGL((nw_align_col<NP, SR, false, NWK_COL_WPE_HI>), dim3(grid), dim3(256), 0, s, a);
+  if (pair) hipLaunchKernelGGL((nw_align_col<NP, SR, false, NWK_COL_WPE_PAIR, true>), dim3(grid), dim3(256), 0, s, a);
+  else if (hi) hipLaunchKernelGGL((nw_align_col<NP, SR, false, NWK_COL_WPE_HI>), dim3(grid), dim3(256), 0, s, a);
   else hipLaunchKernelGGL((nw_align_col<NP, SR, false, NWK_COL_WPE>), dim3(grid), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
 template <int NP, int SR>
-int col_occ(bool hi) {
+int col_occ(bool hi, bool pair) {
   int n = 0;
-  const void* k = hi ? reinterpret_cast<const void*>(&nw_align_col<NP, SR, false, NWK_COL_WPE_HI>)
-                     : reinterpret_cast<const void*>(&nw_align_col<NP, SR, false, NWK_COL_WPE>);
+  const void* k = pair ? reinterpret_cast<const void*>(&nw_align_col<NP, SR, false, NWK_COL_WPE_PAIR, true>)
+                  : hi ? reinterpret_cast<const void*>(&nw_align_col<NP, SR, false, NWK_COL_WPE_HI>)
+                       : reinterpret_cast<const void*>(&nw_align_col<NP, SR, false, NWK_COL_WPE>);
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, 256, 0) != hipSuccess) return 1;
   return n > 0 ? n : 1;
 }
@@ -1239,32 +1358,32 @@ int col_occ(bool hi) {
 
 int bits_sr(int pxy, int pgap);
 
-hipError_t launch_col(const FillArgs& a, int pxy, int pgap, int grid, bool hi, hipStream_t s) {
+hipError_t launch_col(const FillArgs& a, int pxy, int pgap, int grid, bool hi, bool pair, hipStream_t s) {
   const int sr = bits_sr(pxy, pgap);
 #ifdef NWK_COL_ONE  // (development: one instantiation, fast builds)
-  return pgap == 2 && sr == 1 ? col_launch<4, 1>(a, grid, hi, s) : hipErrorInvalidValue;
+  return pgap == 2 && sr == 1 ? col_launch<4, 1>(a, grid, hi, pair, s) : hipErrorInvalidValue;
 #endif
   if (pgap == 1) {
     switch (sr) {
-      case -1: return col_launch<2, -1>(a, grid, hi, s);
-      case 0: return col_launch<2, 0>(a, grid, hi, s);
-      case 1: return col_launch<2, 1>(a, grid, hi, s);
-      default: return col_launch<2, 2>(a, grid, hi, s);
+      case -1: return col_launch<2, -1>(a, grid, hi, pair, s);
+      case 0: return col_launch<2, 0>(a, grid, hi, pair, s);
+      case 1: return col_launch<2, 1>(a, grid, hi, pair, s);
+      default: return col_launch<2, 2>(a, grid, hi, pair, s);
     }
   }
   if (pgap == 2) {
     switch (sr) {
-      case -1: return col_launch<4, -1>(a, grid, hi, s);
-      case 0: return col_launch<4, 0>(a, grid, hi, s);
-      case 1: return col_launch<4, 1>(a, grid, hi, s);
-      case 2: return col_launch<4, 2>(a, grid, hi, s);
-      case 3: return col_launch<4, 3>(a, grid, hi, s);
-      default: return col_launch<4, 4>(a, grid, hi, s);
+      case -1: return col_launch<4, -1>(a, grid, hi, pair, s);
+      case 0: return col_launch<4, 0>(a, grid, hi, pair, s);
+      case 1: return col_launch<4, 1>(a, grid, hi, pair, s);
+      case 2: return col_launch<4, 2>(a, grid, hi, pair, s);
+      case 3: return col_launch<4, 3>(a, grid, hi, pair, s);
+      default: return col_launch<4, 4>(a, grid, hi, pair, s);
     }
   }
   return hipErrorInvalidValue;
 }
 
-int col_blocks_per_cu(int pgap, bool hi) { return pgap == 1 ? col_occ<2, 1>(hi) : col_occ<4, 1>(hi); }
+int col_blocks_per_cu(int pgap, bool hi, bool pair) { return pgap == 1 ? col_occ<2, 1>(hi, pair) : col_occ<4, 1>(hi, pair); }
 
 }  // namespace nwk

@@ -126,9 +126,14 @@ __host__ __device__ inline int pka_sb_lo(int p, int m, int n, int w) {
   return lo <= 0 ? 0 : (int)(lo >> 6);
 }
 
+// kCol: set in a task's band field when the task fills bands band and band + 1
+// as one paired task (nwk_col.hip, two words per lane); launch_col's `pair`
+// selects the instantiation that holds the two-word form
+constexpr int kColTaskPair = 1 << 30;
+
 struct FillArgs {
   const PairDesc* pairs;
-  const int2* tasks;       // {pair index, band}, dependency-ordered
+  const int2* tasks;       // {pair index, band}, dependency-ordered (kCol: band | kColTaskPair)
   int ntasks;
   const uint8_t* codes;    // sequence codes (x rows, y columns)
   const uint32_t* E;       // expanded column codes, 4 per dword
@@ -240,8 +245,8 @@ hipError_t launch_strip(const FillArgs& a, int pxy, int pgap, int grid, hipStrea
 int strip_blocks_per_cu(int pgap, int ring_dwords);
 // kCol (nwk_col.hip)
 // hi: the plain instantiation at NWK_COL_WPE_HI waves per SIMD (not with fuse_fin)
-hipError_t launch_col(const FillArgs& a, int pxy, int pgap, int grid, bool hi, hipStream_t s);
-int col_blocks_per_cu(int pgap, bool hi = false);
+hipError_t launch_col(const FillArgs& a, int pxy, int pgap, int grid, bool hi, bool pair, hipStream_t s);
+int col_blocks_per_cu(int pgap, bool hi = false, bool pair = false);
 // kGotoh (nwk_gotoh.hip): instantiated for a fixed set of (pxy, go, ge)
 bool gotoh_admissible(int pxy, int go, int ge, int alpha);
 int gotoh_granules(int go, int ge);  // granules per 32-column chunk of a band's last row

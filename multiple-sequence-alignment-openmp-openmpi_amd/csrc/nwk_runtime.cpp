@@ -1710,23 +1710,43 @@ int align_work(nwk_ctx* c, std::vector<PairWork>& work, const Scoring& sc, int32
     // kCol: bands trail each other by ~96 steps, so a pair's bands dequeued
     // together run as one short pipeline: pair-major unless NWK_ORDER says otherwise
     if (pl.mode == kCol && order_env < 0) order = c->opts.task_order == 2 ? 1 : 0;
+    // kCol paired tasks (nwk_col.hip, two words per lane): one task fills bands
+    // (0,1), (2,3), .. of a pair, an odd last band stays a single.  Off by
+    // default: a paired task issues ~19% fewer scalar instructions per launch
+    // (C3: SQ_INSTS_SALU 5.31e10 -> 4.31e10, VALU 9.18e10 -> 9.26e10), but its
+    // instantiation needs 128 VGPRs (4 waves/SIMD against 5) and C3 measured
+    // 163.3-164.0 ms per step paired against 142.3-142.6 unpaired
+    // (profiles/r07/ab/col_pair.txt).  NWK_COL_PAIR=1 pairs every kCol batch
+    // without the fused finalize (which has no paired instantiation).
+    static const int col_pair_env = getenv("NWK_COL_PAIR") ? atoi(getenv("NWK_COL_PAIR")) : 0;
+    const bool col_pair = pl.mode == kCol && col_pair_env > 0 &&
+                          !(want_fuse && !(getenv("NWK_AFF_NOTRACE") || getenv("NWK_NOTRACE")));
+    // tasks of pair q, and its b-th task's band field
+    auto ntk = [&](int q) -> int {
+      return col_pair ? (pd[q].nbands + 1) / 2 : (int)tasks_of(pl.mode, pd[q].nbands);
+    };
+    auto tke = [&](int q, int b) -> int2 {
+      if (!(col_pair)) return make_int2(q, b);
+      return make_int2(q, 2 * b + 1 < pd[q].nbands ? (2 * b) | kColTaskPair : 2 * b);
+    };
     if (order == 1) {  // band-major (experiment)
       for (int b = 0; b < maxb; ++b)
         for (int q = 0; q < np; ++q)
-          if (b < tasks_of(pl.mode, pd[q].nbands)) tk[t++] = make_int2(q, b);
+          if (b < ntk(q)) tk[t++] = tke(q, b);
     } else if (order >= 2) {  // groups of `order` pairs, band-major inside a group (experiment)
       for (int g0 = 0; g0 < np; g0 += order) {
         const int g1 = std::min(np, g0 + order);
         int mb = 0;
-        for (int q = g0; q < g1; ++q) mb = std::max(mb, (int)tasks_of(pl.mode, pd[q].nbands));
+        for (int q = g0; q < g1; ++q) mb = std::max(mb, ntk(q));
         for (int b = 0; b < mb; ++b)
           for (int q = g0; q < g1; ++q)
-            if (b < tasks_of(pl.mode, pd[q].nbands)) tk[t++] = make_int2(q, b);
+            if (b < ntk(q)) tk[t++] = tke(q, b);
       }
     } else {
       for (int q = 0; q < np; ++q)
-        for (int b = 0; b < tasks_of(pl.mode, pd[q].nbands); ++b) tk[t++] = make_int2(q, b);
+        for (int b = 0; b < ntk(q); ++b) tk[t++] = tke(q, b);
     }
+    const int64_t ntasks_run = t;  // (< ntasks, the band count, with paired tasks)
     if ((rc = c->d_pairs.ensure(sizeof(PairDesc) * np)) != NWK_OK) return rc;
     if ((rc = c->d_tasks.ensure(sizeof(int2) * ntasks)) != NWK_OK) return rc;
     if ((rc = c->d_oplen.ensure(sizeof(int) * np)) != NWK_OK) return rc;
@@ -1738,7 +1758,7 @@ int align_work(nwk_ctx* c, std::vector<PairWork>& work, const Scoring& sc, int32
     if ((rc = c->h_endij[par].ensure(sizeof(int2) * np)) != NWK_OK) return rc;
     if ((rc = c->h_ops[par].ensure((size_t)ops)) != NWK_OK) return rc;
     HIP_TRY(hipMemcpyAsync(c->d_pairs.p, pd, sizeof(PairDesc) * np, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_tasks.p, tk, sizeof(int2) * ntasks, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_tasks.p, tk, sizeof(int2) * ntasks_run, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->d_ctl.p, 0, 256, c->stream));
     HIP_TRY(hipMemsetAsync(c->d_done.p, 0, sizeof(unsigned) * np, c->stream));
     bool windowed = false;
@@ -1789,7 +1809,7 @@ int align_work(nwk_ctx* c, std::vector<PairWork>& work, const Scoring& sc, int32
     FillArgs fa{};
     fa.pairs = c->d_pairs.as<PairDesc>();
     fa.tasks = c->d_tasks.as<int2>();
-    fa.ntasks = (int)ntasks;
+    fa.ntasks = (int)ntasks_run;
     fa.codes = c->d_codes[pl.kind].as<uint8_t>();
     fa.E = c->d_E[pl.kind].as<uint32_t>();
     fa.sel = pl.mode == kPacked    ? c->d_sel[pl.K0 < 0 ? 1 : 0].as<uint32_t>()
@@ -1939,8 +1959,9 @@ int align_work(nwk_ctx* c, std::vector<PairWork>& work, const Scoring& sc, int32
       // NWK_COL_WPE_HI): C3's 4-rank shard 60.5 -> 48.6 ms; NWK_COL_WPE_HI=0: 4
       static const int wpe_hi_env = getenv("NWK_COL_WPE_HI") ? atoi(getenv("NWK_COL_WPE_HI")) : 1;
       const bool hi = !fuse && wpe_hi_env != 0;
-      const int gcol = col_blocks_per_cu(sc.pgap, hi) * c->cus;
-      HIP_TRY(launch_col(fa, sc.pxy, sc.pgap, (int)std::min<int64_t>(gcol, ceil_div(ntasks, 4)), hi, c->stream));
+      const int gcol = col_blocks_per_cu(sc.pgap, hi, col_pair) * c->cus;
+      HIP_TRY(launch_col(fa, sc.pxy, sc.pgap, (int)std::min<int64_t>(gcol, ceil_div(ntasks_run, 4)), hi, col_pair, c->stream));
+      st.col_paired_tasks += (int)(ntasks - ntasks_run);  // (each paired task stands for two band tasks)
     }
     else if (pl.mode == kBitsStrip)
       HIP_TRY(launch_strip(fa, sc.pxy, sc.pgap, (int)std::min<int64_t>(grid, ceil_div(ntasks, 4)), c->stream));

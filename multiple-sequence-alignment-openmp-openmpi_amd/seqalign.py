@@ -54,7 +54,7 @@ class Stats(ctypes.Structure):
                 ("fill_launches", ctypes.c_int32), ("device_finalized", ctypes.c_int32),
                 ("linear_space_pairs", ctypes.c_int32), ("window_retries", ctypes.c_int32),
                 ("window", ctypes.c_int32), ("guard_checked", ctypes.c_int32),
-                ("guard_reruns", ctypes.c_int32)]
+                ("guard_reruns", ctypes.c_int32), ("col_paired_tasks", ctypes.c_int32)]
 
 
 # Every exported symbol of include/nwk.h with its ctypes signature.
