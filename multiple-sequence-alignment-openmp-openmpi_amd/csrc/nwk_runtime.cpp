@@ -32,6 +32,7 @@
 #include "../../include/nwk.h"
 #include "nwk_internal.h"
 #include "nwk_prof.h"
+#include "nwk_sched.h"
 #include "sha512.h"
 
 using namespace nwk;
@@ -64,6 +65,61 @@ double now_ms() {
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int64_t round_up(int64_t a, int64_t b) { return ceil_div(a, b) * b; }
+
+// Every NWK_* environment variable the align path reads (choose_plan,
+// footprint, plan_job, align_linear_batch, align_work and their helpers), read
+// once per process at the first use.  Why a default is what it is stands at
+// the decision that uses it.  (NWK_VERBOSE, NWK_CU_RESERVE, NWK_POISON* and
+// what nwk_msa reads are read where they are used.)
+struct Knobs {
+  static int num(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
+  static bool set(const char* name) { return getenv(name) != nullptr; }
+  int affpk = num("NWK_AFFPK", 1);                             // =0: never nw_align_pka, keep nw_align_affine
+  int gotoh = num("NWK_GOTOH", 1);                             // =0: no nw_align_gotoh under kernel "auto"
+  int packed = num("NWK_PACKED", 2);                           // =0/1/2: pin nw_align / nw_align_pk / nw_align_pk2 under "auto"
+  bool packed_set = set("NWK_PACKED");                         // present: also keeps small jobs on the pinned kernel
+  int bits_kernel = num("NWK_BITS_KERNEL", 1);                 // =0: no bit-sliced kernels under "auto"
+  int col_seg = num("NWK_COL_SEG", 0);                         // =1: nw_align_col traces in speculative segments
+  int lin_zero = num("NWK_LIN_ZERO", 0);                       // =1/2: linear space re-zeroes its granules / its whole workspace
+  int guard = num("NWK_GUARD", 1);                             // =0: no fill-vs-walk guard
+  bool guard_log = set("NWK_GUARD_LOG");                       // present: report guard re-runs without verbose
+  int strip = num("NWK_STRIP", -1);                            // =1/0: force nw_align_strip / band tasks for kBits jobs
+  int col = num("NWK_COL", -1);                                // =0/1: keep nw_align_bits / force nw_align_col under "auto"
+  int bits_win = num("NWK_BITS_WIN", -1);                      // =0: full storage only; W > 0: that storage window
+  int win_batches = num("NWK_WIN_BATCHES", 0);                 // =b: choose the window that fits the job in b batches
+  int strip_win = num("NWK_STRIP_WIN", 1024);                  // =W: window of strips whose full storage fits (0: full)
+  int col_win = num("NWK_COL_WIN", -1);                        // =0: nw_align_col full storage when it fits; W > 0 forced
+  int sort = num("NWK_SORT", 2);                               // =0/1/2: kPacked2 pair order by cells / m + n / max(m, n) first
+  int spec = num("NWK_SPEC", 2);                               // =E: a speculative segment every E tasks
+  double spec_frac = getenv("NWK_SPEC_FRAC") ? atof(getenv("NWK_SPEC_FRAC")) : -1.0; // =f: the last f of the cells trace speculatively (< 0: by job size)
+  int guess = num("NWK_GUESS", 0);                             // =g: start columns per speculative boundary (0: by job size)
+  int bpc = num("NWK_BPC", 0);                                 // =b: cap on blocks per CU
+  int devhash = num("NWK_DEVHASH", -1);                        // =0/1: host / device finalize under finalize "auto"
+  int host_stream = num("NWK_HOST_STREAM", 1);                 // =0: no streamed host finalize for nw_align_col
+  int poison_batch = num("NWK_POISON_BATCH", -1);              // =byte: fill each batch's matrix region before its launch
+  int col_prio = num("NWK_COL_PRIO", 1);                       // =0: no issue priority for the longest spans
+  int piece_prio = num("NWK_PIECE_PRIO", 1);                   // =0: no issue priority for a streamed shard's first pairs
+  int auto_fuse = num("NWK_AUTO_FUSE", 1);                     // =0: no automatic fused finalize
+  int piece_div = set("NWK_PIECE_DIV") ? std::max(2, num("NWK_PIECE_DIV", 8)) : 8; // =d (>= 2): priority tiers of np / d pairs
+  int piece_top = set("NWK_PIECE_TOP") ? std::min(3, std::max(1, num("NWK_PIECE_TOP", 2))) : 2; // =p (1..3): the first tier's priority
+  int order = num("NWK_ORDER", -1);                            // =0/1/g: task order pair-major / band-major / groups of g
+  int col_pair = num("NWK_COL_PAIR", 0);                       // =1: nw_align_col paired tasks
+  bool notrace = set("NWK_NOTRACE") || set("NWK_AFF_NOTRACE"); // either present: fill only (no walk, guard, fuse, stream)
+  int dbg_badwalk = num("NWK_DBG_BADWALK", 0);                 // =v: FillArgs::dbg_badwalk (tests)
+  int band_prio = num("NWK_BAND_PRIO", 0);                     // =v: FillArgs::band_prio
+  int dbg_corrupt = num("NWK_DBG_CORRUPT", 0);                 // =slot + 1: flip that pair's code of cell (m, n) (tests)
+  bool dbg_corrupt_all = set("NWK_DBG_CORRUPT_ALL");           // present: in every batch, not only the call's first
+  int early_hash = num("NWK_EARLY_HASH", 1);                   // =0 / p: streamed shards hash pairs of prio >= p at once
+  bool watchdog_set = set("NWK_WATCHDOG");                     // present: the kernels keep per-wave progress markers
+  int watchdog = num("NWK_WATCHDOG", 0);                       // =s: dump them and exit when a launch runs longer than s seconds
+  int col_wpe_hi = num("NWK_COL_WPE_HI", 1);                   // =0: plain nw_align_col at 4 waves/SIMD, not 5
+  bool segdump = set("NWK_SEGDUMP");                           // present: the verbose timeline adds segment outcomes
+};
+
+const Knobs& knobs() {
+  static const Knobs k;
+  return k;
+}
 
 // Canonical pair id -> (i, j), skel:122-123.
 inline void pair_ij(int64_t p, int* i, int* j) {
@@ -125,13 +181,11 @@ struct HostBuf {
   template <class T> T* as() const { return static_cast<T*>(p); }
 };
 
-struct PairWork {
+struct PairWork : Footprint {  // (nwk_sched.h: mat_dw, bnd_gr, ops_b, segops_b, segctl_b and the bytes they need())
   int64_t id;       // canonical pair id
   int64_t out;      // index in the caller's output arrays
   int i, j;         // x = seq i (rows), y = seq j (columns)
   int m, n;
-  int64_t mat_dw, bnd_gr, ops_b;  // footprint
-  int64_t segops_b, segctl_b;     // kPacked2 segmented traceback: move buffers, control (flags, info, records)
   int spec;                       // segmented traceback: spec_every
   int nguess;                     // segmented traceback: start columns per speculative boundary
   int64_t njobs;                  // queued extra guesses (spec boundaries x (nguess - 1))
@@ -479,15 +533,13 @@ int choose_plan(const nwk_ctx* c, const Scoring& sc, Plan* pl) {
     // packed band pairs (nw_align_pka) where the int16 window provably holds
     // and the alphabet fits the 4-entry profile; opts.kernel = 1 (unpacked) or
     // NWK_AFFPK=0 keeps nw_align_affine
-    static const int affpk_env = getenv("NWK_AFFPK") ? atoi(getenv("NWK_AFFPK")) : 1;
-    const bool pk = c->opts.kernel != 1 && affpk_env != 0 && c->alpha <= 4 && pka_admissible(sc);
+    const bool pk = c->opts.kernel != 1 && knobs().affpk != 0 && c->alpha <= 4 && pka_admissible(sc);
     pl->mode = pk ? kAffinePk : kAffine;
     // bit-sliced planes (nw_align_gotoh) where an instantiation exists for the
     // scoring (C5's 3/3/1, the linear 3/2 and 5/1 as go = 0, the tests') and the
     // alphabet fits two code planes; opts.kernel 7 asks for it, 1 keeps
     // nw_align_affine, 2 / 3 nw_align_pka; NWK_GOTOH=0 disables it under "auto"
-    static const int gotoh_env = getenv("NWK_GOTOH") ? atoi(getenv("NWK_GOTOH")) : 1;
-    const bool want_gotoh = c->opts.kernel == 7 || (c->opts.kernel == 0 && gotoh_env != 0);
+    const bool want_gotoh = c->opts.kernel == 7 || (c->opts.kernel == 0 && knobs().gotoh != 0);
     if (want_gotoh && gotoh_admissible(sc.pxy, sc.go, sc.ge, c->alpha)) pl->mode = kGotoh;
     pl->bits = 4;          // 4-bit traceback codes
     pl->kind = pk || pl->mode == kGotoh ? 0 : 1;  // profile codes / raw bytes (compare)
@@ -514,8 +566,7 @@ int choose_plan(const nwk_ctx* c, const Scoring& sc, Plan* pl) {
   // (K0, K1 both < 0 or both >= 0).  opts.kernel (or NWK_PACKED=0/1/2 when it is
   // 0) pins nw_align / nw_align_pk / nw_align_pk2 for tests and A/B runs; a
   // packed kernel asked for where it is not exact falls back to nw_align.
-  static const int packed_env = getenv("NWK_PACKED") ? atoi(getenv("NWK_PACKED")) : 2;
-  const int packed = c->opts.kernel > 0 && c->opts.kernel < 4 ? c->opts.kernel - 1 : packed_env;
+  const int packed = c->opts.kernel > 0 && c->opts.kernel < 4 ? c->opts.kernel - 1 : knobs().packed;
   if (pl->mode == kProfile && pl->bits == 4 && packed > 0 && ((pl->K0 < 0) == (pl->K1 < 0)))
     pl->mode = packed == 1 ? kPacked : kPacked2;
   // bit-sliced difference planes (nw_align_bits) wherever they apply: pxy >= 0,
@@ -523,9 +574,8 @@ int choose_plan(const nwk_ctx* c, const Scoring& sc, Plan* pl) {
   // integer kernels, NWK_BITS_KERNEL=0 disables it under "auto" (A/B runs; the
   // driver's NWK_BITS is the storage width, opts.bits).
   // pl->bits keeps the profile kernels' width (the linear-space path uses it).
-  static const int bits_env = getenv("NWK_BITS_KERNEL") ? atoi(getenv("NWK_BITS_KERNEL")) : 1;
   const bool want_bits = c->opts.kernel == 4 || c->opts.kernel == 5 || c->opts.kernel == 6 ||
-                         (c->opts.kernel == 0 && bits_env != 0);
+                         (c->opts.kernel == 0 && knobs().bits_kernel != 0);
   if (want_bits && c->opts.bits == 0 && bits_admissible(pxy, pgap, c->alpha)) pl->mode = kBits;
   // bit-parallel columns (nw_align_col, same domain): opts.kernel 6 (under
   // "auto" use_col decides per job, once the pairs are known)
@@ -639,7 +689,7 @@ int64_t pka_nsb_of(int m, int n, int w) {
 }
 
 // Storage window W of a job whose full matrices exceed the budget (see
-// align_work).  kBits: the widest candidate whose whole job fits `batches`
+// plan_windows).  kBits: the widest candidate whose whole job fits `batches`
 // batches (1 unless NWK_WIN_BATCHES), at least 1024.  kAffinePk: 8192
 // outright -- its paths stray up to ~4.6k columns (profiles/r02/pathdev_c5.txt)
 // and it needs many rounds of band-pair tasks per batch anyway.  need(W) is
@@ -696,8 +746,7 @@ void footprint(PairWork* w, int bits, int mode, bool affine, int gran = 0) {
     // ~500-5000 rows on random sequences (tools/probe/segconv.c), so the pair
     // walk still crosses most of each band and then waits for the segment;
     // measured C4 99.1 vs 91.3 ms per step, big13 26.3 vs 25.9 (r4n).
-    static const int seg_env = getenv("NWK_COL_SEG") ? atoi(getenv("NWK_COL_SEG")) : 0;
-    const bool seg = seg_env != 0 && nb >= 2 && colseg_ok(w->n);
+    const bool seg = knobs().col_seg != 0 && nb >= 2 && colseg_ok(w->n);
     w->spec = seg ? 1 : 0;
     w->nguess = 1;
     w->njobs = 0;
@@ -819,18 +868,13 @@ void parallel_for(int threads, int64_t n, F&& f) {
   for (auto& t : th) t.join();
 }
 
-// Core: aligns `work` (any order) and writes penalties/hashes at work[].out.
-// If strings != nullptr (single-pair API), also returns the alignment rows.
-// The answer-hash chain of skel:159 advanced while later batches still run:
-// results are marked ready by output index (= canonical pair id for a full
-// call) and the chain consumes the ready prefix.
 // caller index q's final result is in place (nwk_align_pairs_poll)
 inline void mark_ready(nwk_ctx* c, int64_t q) {
   if (c->ready_out) c->ready_out[q].store(1, std::memory_order_release);
 }
 
-// Fused finalize: the host side of one batch's streamed records (see the
-// consumer in align_work).  done: 0 running, 1 kernel finished (skip holds
+// The hand-off between a batch and its consumer thread (consume_fused_records,
+// consume_streamed_walks).  done: 0 running, 1 kernel finished (skip holds
 // the window re-runs), 2 abandoned (an error path left align_work).
 struct FusedSync {
   std::atomic<int> done{0};
@@ -881,7 +925,7 @@ int guard_rerun(const nwk_ctx* c, PairWork* w, int endv, int cost, nwk_stats* st
   if (w->guard >= 1)
     return fail(NWK_EKERNEL, "pair %lld (%d x %d): the walked path's cost %d differs from the fill's H(m, n) = %d "
                 "again after a full-storage re-run: %s is wrong", (long long)w->id, w->m, w->n, cost, endv, who);
-  if (c->opts.verbose || getenv("NWK_GUARD_LOG"))
+  if (c->opts.verbose || knobs().guard_log)
     fprintf(stderr, "nwk guard: pair %lld (%d x %d, window %d): walked path cost %d, fill H(m, n) %d -> %s; re-run "
             "with full storage\n", (long long)w->id, w->m, w->n, w->bits_w, cost, endv, who);
   w->guard += 1;
@@ -1005,7 +1049,7 @@ int align_linear_batch(nwk_ctx* c, const Plan& pl0, const Scoring& sc, const Pai
   void* const old_work = c->d_work.p;
   if ((rc = c->d_work.ensure((size_t)work_b)) != NWK_OK) return rc;
   if (c->d_work.p != old_work) c->clean_b = 0;
-  static const int lin_zero = getenv("NWK_LIN_ZERO") ? atoi(getenv("NWK_LIN_ZERO")) : 0;  // debug A/B
+  const int lin_zero = knobs().lin_zero;  // debug A/B
   if (lin_zero == 1) c->clean_b = 0;
   if (lin_zero == 2) HIP_TRY(hipMemsetAsync(c->d_work.p, 0, (size_t)work_b, c->stream));
   if (bnd_need_b > c->clean_b)
@@ -1074,7 +1118,7 @@ int align_linear_batch(nwk_ctx* c, const Plan& pl0, const Scoring& sc, const Pai
   for (int q = 0; q < np; ++q)
     for (int b = 0; b < geo[q].nb; ++b) tk.push_back(make_int2(q, b));
   // fill-vs-walk guard: pass 1 fills every cell and gives each pair's H(m, n)
-  static const int guard_env = getenv("NWK_GUARD") ? atoi(getenv("NWK_GUARD")) : 1;
+  const int guard_env = knobs().guard;
   std::vector<int> endv((size_t)np, 0);
   if (guard_env != 0) {
     if ((rc = c->d_endv.ensure(sizeof(int) * np)) != NWK_OK) return rc;
@@ -1194,25 +1238,43 @@ bool use_strips(const nwk_ctx* c, const std::vector<PairWork>& work, int pgap, b
   return est_s < 0.95 * est_b;
 }
 
-int align_work(nwk_ctx* c, std::vector<PairWork>& work, const Scoring& sc, int32_t* penalties,
-               uint8_t* hashes, std::vector<uint8_t>* a1, std::vector<uint8_t>* a2, Chain* chain = nullptr) {
-  const double t_start = now_ms();
-  nwk_stats st{};
+#define NWK_TRY(expr)                 \
+  do {                                \
+    const int rc_ = (expr);           \
+    if (rc_ != NWK_OK) return rc_;    \
+  } while (0)
+
+// ---- plan_job: what a call decides once, before anything touches the device
+
+struct JobPlan {
   Plan pl;
+  bool bitsy = false;     // a bit-sliced linear kernel: kBits, kBitsStrip or kCol
+  bool gotoh = false;     // kGotoh
+  int ggran = 0;          // kGotoh: granules per 32-column chunk of a band's last row
+  int strip_ring = 0;     // kBitsStrip: LDS hand-off ring per wave (dwords)
+  int bpc = 0, grid = 0;  // blocks per CU and blocks of the persistent launches
+  int fin_mode = -1;      // finalize: 0 host, 1 device, < 0 estimated per batch
+  bool dev_ok = false;    // the device finalize applies to this call
+  int window = 0;         // the first pair's storage window (nwk_stats::window)
+  // the non-degenerate pairs with footprints, windows and speculation set, in
+  // dequeue order.  Capacity for one full-storage re-run of every pair: the
+  // finalize threads hold pointers into it, so it never reallocates (requeue)
+  std::vector<PairWork> dp;
+};
+
+inline void set_footprint(const JobPlan& jp, const Scoring& sc, PairWork* w) {
+  footprint(w, jp.pl.bits, jp.pl.mode, sc.affine, jp.ggran);
+}
+
+// The kernel: choose_plan's, then the choices that depend on the job's pairs.
+void plan_mode(const nwk_ctx* c, const std::vector<PairWork>& work, const Scoring& sc, JobPlan* jp) {
+  Plan& pl = jp->pl;
   choose_plan(c, sc, &pl);
-  if (sc.affine) {
-    if (sc.pxy < 0 || sc.go < 0 || sc.ge < 0)
-      return fail(NWK_EINVAL, "affine gaps need pxy, go, ge >= 0 (got %d, %d, %d)", sc.pxy, sc.go, sc.ge);
-    // H values stay below the kernel's +inf (2^30 - 1) with room for one step
-    for (const auto& w : work)
-      if (((int64_t)w.m + w.n + 2) * ((int64_t)sc.go + sc.ge + sc.pxy) >= (1ll << 29))
-        return fail(NWK_EINVAL, "affine scores of pair (%d x %d) would exceed the int32 range", w.m, w.n);
-  }
   // Small jobs (e.g. one rank's shard of a multi-GPU run): band-pair tasks
   // (1024 rows, 16 cells per lane-step) too few to occupy the wave slots make
   // each pair's row sweep the critical path -- single bands (nw_align_pk,
   // 8 cells per lane-step) sweep a row in about half the time.
-  if (pl.mode == kPacked2 && !getenv("NWK_PACKED") && c->opts.kernel == 0) {
+  if (pl.mode == kPacked2 && !knobs().packed_set && c->opts.kernel == 0) {
     int64_t t2 = 0;
     for (const auto& w : work)
       if (w.m > 0 && w.n > 0) t2 += ceil_div(w.m, 2 * kBandRows);
@@ -1220,11 +1282,9 @@ int align_work(nwk_ctx* c, std::vector<PairWork>& work, const Scoring& sc, int32
   }
   // nw_align_bits as rolling strips (kBitsStrip): NWK_STRIP / opts.kernel 5
   // force them (1) or band tasks (0); by default use_strips decides
-  int strip_ring = 0;
   if (pl.mode == kBits) {
-    static const int strip_env = getenv("NWK_STRIP") ? atoi(getenv("NWK_STRIP")) : -1;
-    const int want = c->opts.kernel == 5 ? 1 : c->opts.kernel == 4 ? 0 : strip_env;
-    if (want != 0 && use_strips(c, work, sc.pgap, want == 1, &strip_ring)) pl.mode = kBitsStrip;
+    const int want = c->opts.kernel == 5 ? 1 : c->opts.kernel == 4 ? 0 : knobs().strip;
+    if (want != 0 && use_strips(c, work, sc.pgap, want == 1, &jp->strip_ring)) pl.mode = kBitsStrip;
   }
   // nw_align_col under "auto", wherever the bits kernels apply: a pair costs its
   // span n + ~100 per band there against n + 2112 per band for nw_align_bits,
@@ -1236,192 +1296,165 @@ int align_work(nwk_ctx* c, std::vector<PairWork>& work, const Scoring& sc, int32
   // 4 waves/SIMD and a device finalize after the launch: 160 vs 153 ms).
   // NWK_COL=0 keeps nw_align_bits (A/B runs), NWK_STRIP=1 forces strips.
   if ((pl.mode == kBits || pl.mode == kBitsStrip) && c->opts.kernel == 0) {
-    static const int col_env = getenv("NWK_COL") ? atoi(getenv("NWK_COL")) : -1;
-    static const bool strip_forced = getenv("NWK_STRIP") && atoi(getenv("NWK_STRIP")) == 1;
+    const int col_env = knobs().col;
+    const bool strip_forced = knobs().strip == 1;
     const bool col = col_env == 1 || (col_env < 0 && !strip_forced);
     if (col) pl.mode = kCol;
   }
-  const bool bitsy = pl.mode == kBits || pl.mode == kBitsStrip || pl.mode == kCol;
-  bool gotoh = pl.mode == kGotoh;
-  int ggran = gotoh ? gotoh_granules(sc.go, sc.ge) : 0;
-  st.bits = bitsy ? 2 : pl.bits;
-  st.mode = pl.mode;
-  int rc;
-  HIP_TRY(hipSetDevice(c->device));
+  jp->bitsy = pl.mode == kBits || pl.mode == kBitsStrip || pl.mode == kCol;
+  jp->gotoh = pl.mode == kGotoh;
+  jp->ggran = jp->gotoh ? gotoh_granules(sc.go, sc.ge) : 0;
+}
 
-  // Degenerate pairs (m == 0 or n == 0) have no DP cells: prefix only.
-  // (capacity for one full-storage re-run of every pair: a kBits windowed pair
-  // whose path leaves its window is appended once, and the async finalize
-  // holds pointers into dp, so it must never reallocate)
-  std::vector<PairWork> dp;
-  dp.reserve(4 * work.size() + 16);
-  for (auto& w : work) {
-    st.cells += (double)w.m * (double)w.n;
-    if (w.m == 0 || w.n == 0) {
-      Finalized f;
-      const uint8_t* x = c->seqs.data() + c->off[w.i];
-      const uint8_t* y = c->seqs.data() + c->off[w.j];
-      finalize_pair(x, w.m, y, w.n, sc, nullptr, 0, w.m, w.n, &f, a1, a2);
-      penalties[w.out] = f.penalty;
-      memcpy(hashes + 64 * w.out, f.hash, 64);
-      if (chain) chain->ready[w.out] = 1;
-      mark_ready(c, w.out);
-    } else {
-      footprint(&w, pl.bits, pl.mode, sc.affine, ggran);
-      dp.push_back(w);
-    }
+// nw_align_gotoh stores whole 2048-row bands plus their 2080-step skew, so a
+// short pair costs more than on the band-pair kernels: a pair that does not
+// fit the budget even at its 8192-column window runs the job on nw_align_pka
+// (or nw_align_affine) instead.
+void plan_gotoh_fit(const nwk_ctx* c, const Scoring& sc, JobPlan* jp) {
+  if (!jp->gotoh) return;
+  bool fits = true;
+  for (const auto& w : jp->dp) {
+    PairWork t = w;
+    t.bits_w = 8192;
+    set_footprint(*jp, sc, &t);
+    fits = fits && t.need() <= c->budget;
   }
-  // nw_align_gotoh stores whole 2048-row bands plus their 2080-step skew, so a
-  // short pair costs more than on the band-pair kernels: a pair that does not
-  // fit the budget even at its 8192-column window runs the job on nw_align_pka
-  // (or nw_align_affine) instead.
-  if (gotoh) {
-    bool fits = true;
-    for (const auto& w : dp) {
-      PairWork t = w;
-      t.bits_w = 8192;
-      footprint(&t, pl.bits, pl.mode, sc.affine, ggran);
-      fits = fits && t.mat_dw * 4 + t.bnd_gr * 8 + 3 * t.ops_b + 8192 <= c->budget;
+  if (fits) return;
+  const bool pk = c->alpha <= 4 && pka_admissible(sc);
+  jp->pl.mode = pk ? kAffinePk : kAffine;
+  jp->pl.kind = pk ? 0 : 1;
+  jp->gotoh = false;
+  jp->ggran = 0;
+  for (auto& w : jp->dp) set_footprint(*jp, sc, &w);
+}
+
+// kBits windowed storage.  When the job's full 2-bit matrices exceed the
+// workspace, store only the steps within W columns of each pair's diagonal
+// j = i n / m, W the widest candidate that fits the job in one batch (at
+// least 1024).  Paths of random C3 pairs stay within ~1.2k columns of it
+// (tools/pathdev.py); a path that leaves its window is detected by the
+// traceback and the pair re-runs with full storage (collect_retries),
+// so results never depend on W.  NWK_BITS_WIN: 0 off, W > 0 forced.
+//
+// kAffinePk (nw_align_pka) the same way, per 64-step super-block of a band
+// pair.  Its bands need many rounds of tasks per wave slot to run free of
+// the band-pair chains (a band pair dequeued right behind the one above
+// waits on it), which only a window gives at C5's size (full storage: 13
+// pairs per batch).  Affine paths stray further (C5 pairs: up to ~4.6k
+// columns, profiles/r02/pathdev_c5.txt), so it keeps W = 8192 and takes
+// more batches (C5: 4 of ~124 pairs, ~12 rounds of wave slots each).
+void plan_windows(const nwk_ctx* c, const Scoring& sc, JobPlan* jp) {
+  const Plan& pl = jp->pl;
+  std::vector<PairWork>& dp = jp->dp;
+  const int win_env = knobs().bits_win;
+  if (!((jp->bitsy || pl.mode == kAffinePk || jp->gotoh) && !dp.empty() && win_env != 0)) return;
+  auto total_b = [&]() {
+    Footprint sum{};
+    for (const auto& w : dp) sum += w;
+    return sum.need();
+  };
+  auto set_w = [&](int W) {
+    for (auto& w : dp) {
+      w.bits_w = W;
+      set_footprint(*jp, sc, &w);
     }
-    if (!fits) {
-      const bool pk = c->alpha <= 4 && pka_admissible(sc);
-      pl.mode = pk ? kAffinePk : kAffine;
-      pl.kind = pk ? 0 : 1;
-      st.mode = pl.mode;
-      gotoh = false;
-      ggran = 0;
-      for (auto& w : dp) footprint(&w, pl.bits, pl.mode, sc.affine, ggran);
-    }
-  }
-  if (!dp.empty()) {
-    if ((rc = build_encoding(c, pl.kind)) != NWK_OK) return rc;
-    if ((bitsy || gotoh) && (rc = build_yw(c)) != NWK_OK) return rc;
-    if ((pl.mode == kPacked || band_pairs(pl.mode)) &&
-        (rc = build_sel(c, pl.K0 < 0 ? 1 : 0, band_pairs(pl.mode) ? 64 : 1)) != NWK_OK)
-      return rc;
-  }
-  // kBits windowed storage.  When the job's full 2-bit matrices exceed the
-  // workspace, store only the steps within W columns of each pair's diagonal
-  // j = i n / m, W the widest candidate that fits the job in one batch (at
-  // least 1024).  Paths of random C3 pairs stay within ~1.2k columns of it
-  // (tools/pathdev.py); a path that leaves its window is detected by the
-  // traceback and the pair re-runs with full storage (the retry list below),
-  // so results never depend on W.  NWK_BITS_WIN: 0 off, W > 0 forced.
+  };
+  int W = win_env > 0 ? win_env : 0;
+  if (W == 0 && total_b() > c->budget)
+    W = choose_window(pl.mode, knobs().win_batches, c->budget, [&](int wc) {
+      set_w(wc);
+      return total_b();
+    });
+  // Strips keep a 1024-column window even when full storage fits: below one
+  // band's height a window writes only the lane words near the diagonal
+  // (bits_lane_window), about half of them at 1024 -- C4's 8-rank shard
+  // fits in full, and full storage wrote ~6 TB/s of HBM at 4 waves/SIMD.
+  // Random 8k pairs' paths stay within ~400 columns (pathdev_c4.txt); a pair
+  // whose path leaves re-runs in full.  NWK_STRIP_WIN overrides (0: full).
+  if (W == 0 && pl.mode == kBitsStrip) W = knobs().strip_win;
+  set_w(W);
+  // nw_align_col stores 512 B per wave-step; at full storage a batch of many
+  // concurrent bands writes faster than HBM takes it (C3's 8-rank shard and
+  // big13 fit in full and wrote ~4-6 TB/s), so it keeps a window even when
+  // full storage fits: per pair W = 2.5 x the paths' expected stray from the
+  // diagonal, ~400 (n / 8000)^(2/3) columns for random sequences (max |dev|
+  // over sampled pairs: 361 at C4's 8k, 1165 at C3's 50k,
+  // profiles/r02/pathdev_*.txt), at least 1024 and at most a budget-forced W.
+  // A path that strays further re-runs with full storage.  NWK_COL_WIN:
+  // 0 = full storage when it fits, W > 0 forced.
   //
-  // kAffinePk (nw_align_pka) the same way, per 64-step super-block of a band
-  // pair.  Its bands need many rounds of tasks per wave slot to run free of
-  // the band-pair chains (a band pair dequeued right behind the one above
-  // waits on it), which only a window gives at C5's size (full storage: 13
-  // pairs per batch).  Affine paths stray further (C5 pairs: up to ~4.6k
-  // columns, profiles/r02/pathdev_c5.txt), so it keeps W = 8192 and takes
-  // more batches (C5: 4 of ~124 pairs, ~12 rounds of wave slots each).
-  static const int win_env = getenv("NWK_BITS_WIN") ? atoi(getenv("NWK_BITS_WIN")) : -1;
-  static const int winb_env = getenv("NWK_WIN_BATCHES") ? atoi(getenv("NWK_WIN_BATCHES")) : 0;
-  if ((bitsy || pl.mode == kAffinePk || gotoh) && !dp.empty() && win_env != 0) {
-    auto total_b = [&]() {
-      int64_t mat = 0, bnd = 0, ops = 0;
-      int64_t seg = 0;
-      for (const auto& w : dp) mat += w.mat_dw, bnd += w.bnd_gr, ops += w.ops_b, seg += w.segops_b + w.segctl_b;
-      return mat * 4 + bnd * 8 + 3 * ops + seg + 8192;
-    };
-    auto set_w = [&](int W) {
-      for (auto& w : dp) {
-        w.bits_w = W;
-        footprint(&w, pl.bits, pl.mode, sc.affine, ggran);
-      }
-    };
-    int W = win_env > 0 ? win_env : 0;
-    if (W == 0 && total_b() > c->budget)
-      W = choose_window(pl.mode, winb_env, c->budget, [&](int wc) {
-        set_w(wc);
-        return total_b();
-      });
-    // Strips keep a 1024-column window even when full storage fits: below one
-    // band's height a window writes only the lane words near the diagonal
-    // (bits_lane_window), about half of them at 1024 -- C4's 8-rank shard
-    // fits in full, and full storage wrote ~6 TB/s of HBM at 4 waves/SIMD.
-    // Random 8k pairs' paths stay within ~400 columns (pathdev_c4.txt); a pair
-    // whose path leaves re-runs in full.  NWK_STRIP_WIN overrides (0: full).
-    static const int strip_win_env = getenv("NWK_STRIP_WIN") ? atoi(getenv("NWK_STRIP_WIN")) : 1024;
-    if (W == 0 && pl.mode == kBitsStrip) W = strip_win_env;
-    set_w(W);
-    // nw_align_col stores 512 B per wave-step; at full storage a batch of many
-    // concurrent bands writes faster than HBM takes it (C3's 8-rank shard and
-    // big13 fit in full and wrote ~4-6 TB/s), so it keeps a window even when
-    // full storage fits: per pair W = 2.5 x the paths' expected stray from the
-    // diagonal, ~400 (n / 8000)^(2/3) columns for random sequences (max |dev|
-    // over sampled pairs: 361 at C4's 8k, 1165 at C3's 50k,
-    // profiles/r02/pathdev_*.txt), at least 1024 and at most a budget-forced W.
-    // A path that strays further re-runs with full storage.  NWK_COL_WIN:
-    // 0 = full storage when it fits, W > 0 forced.
-    //
-    // Only a job whose full storage would be written faster than ~4 TB/s takes
-    // it: estimated fill time max(cells / 32k GCUPS, longest pair span x 0.3 us
-    // per wave-step under load), span = n + 100 per band.  A job bound by one
-    // long pair's span (big13: 94k steps) writes ~2.5 TB/s in full and keeps
-    // full storage -- related sequences' paths stray far from the diagonal
-    // (big13: 2.9k-50k columns, profiles/r04/pathdev_big13.txt), so a window
-    // there sends nearly every pair to the re-run.
-    static const int col_win_env = getenv("NWK_COL_WIN") ? atoi(getenv("NWK_COL_WIN")) : -1;
-    bool col_wb = col_win_env > 0;
-    if (pl.mode == kCol && col_win_env < 0) {
-      double cells = 0, bytes = 0, span = 0;
-      for (const auto& w : dp) {
-        cells += (double)w.m * w.n;
-        bytes += (double)w.m * w.n / 4;
-        span = std::max(span, (double)w.n + 100.0 * (double)ceil_div(w.m, kBitsRows));
-      }
-      col_wb = bytes / std::max(cells / 3.2e13, span * 3.0e-7) > 4e12;
+  // Only a job whose full storage would be written faster than ~4 TB/s takes
+  // it: estimated fill time max(cells / 32k GCUPS, longest pair span x 0.3 us
+  // per wave-step under load), span = n + 100 per band.  A job bound by one
+  // long pair's span (big13: 94k steps) writes ~2.5 TB/s in full and keeps
+  // full storage -- related sequences' paths stray far from the diagonal
+  // (big13: 2.9k-50k columns, profiles/r04/pathdev_big13.txt), so a window
+  // there sends nearly every pair to the re-run.
+  const int col_win_env = knobs().col_win;
+  bool col_wb = col_win_env > 0;
+  if (pl.mode == kCol && col_win_env < 0) {
+    double cells = 0, bytes = 0, span = 0;
+    for (const auto& w : dp) {
+      cells += (double)w.m * w.n;
+      bytes += (double)w.m * w.n / 4;
+      span = std::max(span, (double)w.n + 100.0 * (double)ceil_div(w.m, kBitsRows));
     }
-    if (pl.mode == kCol && win_env < 0 && col_wb) {
-      for (auto& w : dp) {
-        const double est = 400.0 * std::pow(std::max(w.m, w.n) / 8000.0, 2.0 / 3.0);
-        int wc = col_win_env > 0 ? col_win_env : (int)round_up(std::max<int64_t>(1024, (int64_t)(2.5 * est)), 256);
-        if (W > 0) wc = std::min(wc, W);
-        w.bits_w = wc;
-        footprint(&w, pl.bits, pl.mode, sc.affine, ggran);
-      }
+    col_wb = bytes / std::max(cells / 3.2e13, span * 3.0e-7) > 4e12;
+  }
+  if (pl.mode == kCol && win_env < 0 && col_wb) {
+    for (auto& w : dp) {
+      const double est = 400.0 * std::pow(std::max(w.m, w.n) / 8000.0, 2.0 / 3.0);
+      int wc = col_win_env > 0 ? col_win_env : (int)round_up(std::max<int64_t>(1024, (int64_t)(2.5 * est)), 256);
+      if (W > 0) wc = std::min(wc, W);
+      w.bits_w = wc;
+      set_footprint(*jp, sc, &w);
     }
   }
-  st.window = dp.empty() ? 0 : dp[0].bits_w;
-  // Largest first (LPT inside the device; longest bands dequeued first).
-  // kPacked2 (NWK_SORT != 0): by traceback length m + n first, so the pairs
-  // filled last -- whose traces form the kernel's tail -- are the shortest to trace.
-  // NWK_SORT: 1 = m + n, 2 = max(m, n) (wide pairs merge their segments slowest), 0 = cells only
-  static const int sort_trace = getenv("NWK_SORT") ? atoi(getenv("NWK_SORT")) : 2;
-  const int by_trace = pl.mode == kPacked2 ? sort_trace : 0;
-  std::sort(dp.begin(), dp.end(), [by_trace](const PairWork& a, const PairWork& b) {
+}
+
+// Largest first (LPT inside the device; longest bands dequeued first).
+// kPacked2 (NWK_SORT != 0): by traceback length m + n first, so the pairs
+// filled last -- whose traces form the kernel's tail -- are the shortest to trace.
+// NWK_SORT: 1 = m + n, 2 = max(m, n) (wide pairs merge their segments slowest), 0 = cells only
+void plan_pair_order(JobPlan* jp) {
+  const int by_trace = jp->pl.mode == kPacked2 ? knobs().sort : 0;
+  std::sort(jp->dp.begin(), jp->dp.end(), [by_trace](const PairWork& a, const PairWork& b) {
     const int ka = by_trace == 1 ? a.m + a.n : std::max(a.m, a.n), kb = by_trace == 1 ? b.m + b.n : std::max(b.m, b.n);
     if (by_trace && ka != kb) return ka > kb;
     const double ca = (double)a.m * a.n, cb = (double)b.m * b.n;
     if (ca != cb) return ca > cb;
     return a.id < b.id;
   });
-  // Segmented traceback (kPacked2): only the pairs dequeued last -- the last
-  // NWK_SPEC_FRAC (default 0.35) of the cells -- trace speculatively (a
-  // segment every NWK_SPEC tasks, default 2); earlier pairs' whole-pair
-  // traces overlap the remaining fill anyway.
-  if (segmented(pl.mode)) {
-    // small jobs (nw_align_pk chosen above): every pair's trace is on the
-    // critical path -> speculate everywhere with NWK_GUESS start columns per
-    // boundary (default 8); large jobs: only the tail pairs
-    const bool small = pl.mode == kPacked;
-    static const int spec_env = getenv("NWK_SPEC") ? atoi(getenv("NWK_SPEC")) : 2;
-    static const double frac_env = getenv("NWK_SPEC_FRAC") ? atof(getenv("NWK_SPEC_FRAC")) : -1.0;
-    static const int guess_env = getenv("NWK_GUESS") ? atoi(getenv("NWK_GUESS")) : 0;
-    const double frac = frac_env >= 0 ? frac_env : small ? 1.0 : 0.35;
-    const int NG = guess_env > 0 ? guess_env : small ? 8 : 1;
-    double tot = 0, acc = 0;
-    for (const auto& w : dp) tot += (double)w.m * w.n;
-    for (auto& w : dp) {
-      const bool on = acc >= (1.0 - frac) * tot - 0.5;
-      seg_footprint(&w, pl.mode, on ? std::max(0, spec_env) * (pl.mode == kPacked ? 2 : 1) : 0, NG);
-      acc += (double)w.m * w.n;
-    }
+}
+
+// Segmented traceback (kPacked, kPacked2): only the pairs dequeued last -- the
+// last NWK_SPEC_FRAC (default 0.35) of the cells -- trace speculatively (a
+// segment every NWK_SPEC tasks, default 2); earlier pairs' whole-pair
+// traces overlap the remaining fill anyway.
+void plan_speculation(JobPlan* jp) {
+  const Plan& pl = jp->pl;
+  if (!segmented(pl.mode)) return;
+  // small jobs (nw_align_pk chosen in plan_mode): every pair's trace is on the
+  // critical path -> speculate everywhere with NWK_GUESS start columns per
+  // boundary (default 8); large jobs: only the tail pairs
+  const bool small = pl.mode == kPacked;
+  const double frac = knobs().spec_frac >= 0 ? knobs().spec_frac : small ? 1.0 : 0.35;
+  const int NG = knobs().guess > 0 ? knobs().guess : small ? 8 : 1;
+  double tot = 0, acc = 0;
+  for (const auto& w : jp->dp) tot += (double)w.m * w.n;
+  for (auto& w : jp->dp) {
+    const bool on = acc >= (1.0 - frac) * tot - 0.5;
+    seg_footprint(&w, pl.mode, on ? std::max(0, knobs().spec) * (pl.mode == kPacked ? 2 : 1) : 0, NG);
+    acc += (double)w.m * w.n;
   }
+}
+
+// Blocks per CU (waves per SIMD) and the grid of the persistent launches.
+void plan_waves(const nwk_ctx* c, const Scoring& sc, JobPlan* jp) {
+  const Plan& pl = jp->pl;
   int bpc = pl.mode == kBits        ? bits_blocks_per_cu(sc.pgap)
             : pl.mode == kCol       ? col_blocks_per_cu(sc.pgap)
-            : pl.mode == kBitsStrip ? strip_blocks_per_cu(sc.pgap, strip_ring)
+            : pl.mode == kBitsStrip ? strip_blocks_per_cu(sc.pgap, jp->strip_ring)
                                     : fill_blocks_per_cu(pl.mode, pl.bits);
   // waves per SIMD: nw_align_pk2 measured best at 2 (band chains run at the
   // pace of their slowest member; more waves per SIMD only add waiting);
@@ -1431,961 +1464,1225 @@ int align_work(nwk_ctx* c, std::vector<PairWork>& work, const Scoring& sc, int32
   // (profiles/r01/ab_affine_bpc.json)
   if (pl.mode == kAffine) bpc = std::min(bpc, 2);
   if (pl.mode == kAffinePk) bpc = std::min(bpc, 2);
-  if (gotoh) bpc = gotoh_blocks_per_cu(sc.pxy, sc.go, sc.ge);
-  static const int bpc_cap = getenv("NWK_BPC") ? atoi(getenv("NWK_BPC")) : 0;
-  if (bpc_cap > 0) bpc = std::min(bpc_cap, bitsy || gotoh ? bpc : fill_blocks_per_cu(pl.mode, pl.bits));
-  const int grid = bpc * c->cus;
-  float ms = 0;
+  if (jp->gotoh) bpc = gotoh_blocks_per_cu(sc.pxy, sc.go, sc.ge);
+  const int bpc_cap = knobs().bpc;
+  if (bpc_cap > 0) bpc = std::min(bpc_cap, jp->bitsy || jp->gotoh ? bpc : fill_blocks_per_cu(pl.mode, pl.bits));
+  jp->bpc = bpc;
+  jp->grid = bpc * c->cus;
+}
 
-  // at most one finalize in flight; joined on every exit path
-  struct Joiner {
-    std::thread t;
-    void start(std::function<void()> f) { t = std::thread(std::move(f)); }
-    void join() { if (t.joinable()) t.join(); }
-    ~Joiner() { join(); }
-  } fin;
-  // Device finalize (nw_hash) when no input byte is '_' and the
-  // batch has enough pairs for one lane per row to beat the host threads:
-  // est. device ms ~ 0.007 per 128-byte block of the longest row (per wave
-  // slot round), host ~ 350 bytes/us per thread.  NWK_DEVHASH=0/1 forces.
-  static const int devhash_env = getenv("NWK_DEVHASH") ? atoi(getenv("NWK_DEVHASH")) : -1;
-  const int fin_mode = c->opts.finalize == 1 ? 0 : c->opts.finalize >= 2 ? 1 : devhash_env;
-  const bool dev_ok = a1 == nullptr && !c->has_us && fin_mode != 0;
-  if (dev_ok && !dp.empty() && (rc = build_encoding(c, 1)) != NWK_OK) return rc;
-  size_t pos = 0;
-  // a pair re-runs in a later batch: with full storage (windowed storage whose
-  // walk left the window, or a walk the fill-vs-walk guard rejected); the
-  // affine path has no linear-space fallback, so there it takes the widest
-  // doubled window that fits the budget when full storage does not
-  auto requeue = [&](PairWork w) -> int {
-    const int old_w = w.bits_w;
-    w.bits_w = 0;
-    footprint(&w, pl.bits, pl.mode, sc.affine, ggran);
-    auto need = [](const PairWork& x) {
-      return x.mat_dw * 4 + x.bnd_gr * 8 + 3 * x.ops_b + x.segops_b + x.segctl_b + 8192;
-    };
-    if ((pl.mode == kAffinePk || gotoh) && need(w) > c->budget) {
-      int nw = 0;
-      for (int64_t cw = 2 * (int64_t)std::max(old_w, 1); cw < (1 << 30); cw *= 2) {
-        PairWork t = w;
-        t.bits_w = (int)cw;
-        footprint(&t, pl.bits, pl.mode, sc.affine, ggran);
-        if (need(t) > c->budget) break;
-        nw = (int)cw;
-        if (t.mat_dw >= w.mat_dw) break;  // as wide as full storage
-      }
-      if (nw == 0)
-        return fail(NWK_ENOMEM, "pair %lld (%d x %d): its traceback left the %d-column storage window and "
-                    "neither full storage (%lld B) nor a %d-column window fits the HBM budget %lld",
-                    (long long)w.id, w.m, w.n, old_w, (long long)need(w), 2 * old_w, (long long)c->budget);
-      w.bits_w = nw;
-      footprint(&w, pl.bits, pl.mode, sc.affine, ggran);
+// Plans the call for `work` (strings: the single-pair API wants the alignment
+// rows).  No device call, no output: only *jp.
+int plan_job(const nwk_ctx* c, const std::vector<PairWork>& work, const Scoring& sc, bool strings, JobPlan* jp) {
+  if (sc.affine) {
+    if (sc.pxy < 0 || sc.go < 0 || sc.ge < 0)
+      return fail(NWK_EINVAL, "affine gaps need pxy, go, ge >= 0 (got %d, %d, %d)", sc.pxy, sc.go, sc.ge);
+    // H values stay below the kernel's +inf (2^30 - 1) with room for one step
+    for (const auto& w : work)
+      if (((int64_t)w.m + w.n + 2) * ((int64_t)sc.go + sc.ge + sc.pxy) >= (1ll << 29))
+        return fail(NWK_EINVAL, "affine scores of pair (%d x %d) would exceed the int32 range", w.m, w.n);
+  }
+  plan_mode(c, work, sc, jp);
+  // (degenerate pairs, m == 0 or n == 0, have no DP cells: align_work finalizes them)
+  jp->dp.reserve(4 * work.size() + 16);
+  for (const auto& w : work) {
+    if (w.m == 0 || w.n == 0) continue;
+    jp->dp.push_back(w);
+    set_footprint(*jp, sc, &jp->dp.back());
+  }
+  plan_gotoh_fit(c, sc, jp);
+  plan_windows(c, sc, jp);
+  jp->window = jp->dp.empty() ? 0 : jp->dp[0].bits_w;
+  plan_pair_order(jp);
+  plan_speculation(jp);
+  plan_waves(c, sc, jp);
+  // Device finalize (nw_hash) when no input byte is '_' (and per
+  // batch, estimate_finalize).  NWK_DEVHASH=0/1 forces.
+  jp->fin_mode = c->opts.finalize == 1 ? 0 : c->opts.finalize >= 2 ? 1 : knobs().devhash;
+  jp->dev_ok = !strings && !c->has_us && jp->fin_mode != 0;
+  return NWK_OK;
+}
+
+// ---- results and the threads that publish them
+
+// Where a call's results go.  store() writes a pair's penalty and hash;
+// publish() then hands the pair on: to the answer-hash chain (its schedule
+// before its ready flag: the chain takes a ready pair at once) and to a
+// poller.  A pair that re-runs (skipped) is never published.  The chain's
+// advance() is the caller's, once per sweep over many pairs.
+struct Results {
+  nwk_ctx* c;
+  int32_t* penalties;
+  uint8_t* hashes;
+  Chain* chain;
+  void store(int64_t out, int32_t penalty, const uint8_t* hash) const {
+    penalties[out] = penalty;
+    memcpy(hashes + 64 * out, hash, 64);
+  }
+  // prepare: compute the chain schedule here (the consumer threads, off the
+  // chain's critical path); otherwise advance() computes it
+  void publish(int64_t out, bool prepare) const {
+    if (chain) {
+      if (prepare) chain->prepare(out);
+      chain->ready[out] = 1;
     }
-    if (dp.size() == dp.capacity())  // the async finalize holds pointers into dp
-      return fail(NWK_ENOMEM, "pair %lld: too many re-runs", (long long)w.id);
-    dp.push_back(w);
-    return NWK_OK;
-  };
-  // fill-vs-walk guard mismatches found by the host finalize threads (dp index, H(m, n), path cost)
-  GuardLog gl;
-  static const int guard_env = getenv("NWK_GUARD") ? atoi(getenv("NWK_GUARD")) : 1;
-  const bool guard_on = guard_env != 0;
-  std::vector<std::shared_ptr<FusedSync>> fused_all;  // streamed batches (checked after the last join)
+    mark_ready(c, out);
+  }
+};
+
+// at most one finalize thread in flight; joined on every exit path
+struct Joiner {
+  std::thread t;
+  void start(std::function<void()> f) { t = std::thread(std::move(f)); }
+  void join() { if (t.joinable()) t.join(); }
+  ~Joiner() { join(); }
+};
+
+// Everything one align_work call owns that a finalize thread may touch.
+struct Job {
+  nwk_ctx* c;
+  const Scoring sc;
+  const Results res;
+  std::vector<uint8_t>* a1;  // single-pair API: the alignment rows (else nullptr)
+  std::vector<uint8_t>* a2;
+  JobPlan plan;              // plan.dp: the threads hold pointers into it
+  nwk_stats st{};
+  GuardLog gl;  // fill-vs-walk guard mismatches found by the host finalize threads (dp index, H(m, n), path cost)
+  std::vector<std::shared_ptr<FusedSync>> fused_all;       // streamed batches (checked after the last join)
   double h_setup = 0, h_sync = 0, h_join = 0, h_last = 0;  // host phases (verbose)
-  const bool lin_all = c->opts.linear_space > 0 && !sc.affine;  // (tests: every pair through f2)
-  for (;;) {
-  while (pos < dp.size()) {
-    // ---- form a batch that fits the HBM budget
-    size_t end = pos;
-    bool lin_one = false;
-    int64_t mat = 0, bnd = 0, ops = 0, segops = 0, segctl = 0;
-    while (end < dp.size()) {
-      const PairWork& w = dp[end];
-      const int64_t need = (mat + w.mat_dw) * 4 + (bnd + w.bnd_gr) * 8 + 3 * (ops + w.ops_b) + segops + w.segops_b +
-                           segctl + w.segctl_b + 8192;
-      if ((need > c->budget || lin_all) && end > pos) break;
-      if (need > c->budget || lin_all) {  // a pair whose matrix does not fit: linear-space traceback (f2)
-        if (c->opts.linear_space < 0 || sc.affine)
-          return fail(NWK_ENOMEM, "pair %lld (%d x %d) needs %lld bytes > HBM budget %lld", (long long)w.id,
-                      w.m, w.n, (long long)need, (long long)c->budget);
-        lin_one = true;
-        break;
-      }
-      mat += w.mat_dw; bnd += w.bnd_gr; ops += w.ops_b; segops += w.segops_b; segctl += w.segctl_b;
-      ++end;
-    }
-    if (lin_one) {
-      fin.join();
-      // forced (tests): as many pairs per linear-space batch as fit; automatic:
-      // the pair that does not fit, alone, with as many bands per group as fit
-      const Plan lpl = lin_plan(pl);
-      const int G = lin_all ? c->opts.linear_space : lin_auto_groups(c, lpl, dp[pos]);
-      if (G < 1)
-        return fail(NWK_ENOMEM, "pair (%d x %d): boundary rows and two bands exceed the HBM budget %lld", dp[pos].m,
-                    dp[pos].n, (long long)c->budget);
-      size_t lend = pos + 1;
-      int64_t used = lin_geo(lpl, dp[pos], G).bytes;
-      while (lin_all && lend < dp.size()) {
-        const int64_t more = lin_geo(lpl, dp[lend], G).bytes;
-        if (used + more + 8192 > c->budget) break;
-        used += more;
-        ++lend;
-      }
-      const int nl = (int)(lend - pos);
-      std::vector<Finalized> fs((size_t)nl);
-      if ((rc = align_linear_batch(c, pl, sc, dp.data() + pos, nl, G, fs.data(), a1, a2, &st)) != NWK_OK) return rc;
-      for (int q = 0; q < nl; ++q) {
-        const PairWork& w = dp[pos + q];
-        penalties[w.out] = fs[q].penalty;
-        memcpy(hashes + 64 * w.out, fs[q].hash, 64);
-        if (chain) chain->ready[w.out] = 1;
-        mark_ready(c, w.out);
-      }
-      if (chain) chain->advance();
-      pos = lend;
-      continue;
-    }
-    const int np = (int)(end - pos);
-    const double tb0 = now_ms();
-    bool devhash = false;
-    if (dev_ok) {
-      double bytes = 0, maxlen = 0;
-      for (size_t q = pos; q < end; ++q) {
-        bytes += 2.0 * (dp[q].m + dp[q].n);
-        maxlen = std::max(maxlen, (double)(dp[q].m + dp[q].n));
-      }
-      const double waves = 2.0 * np / 64.0, slots = 8.0 * c->cus;
-      // ~0.007 ms per 128-byte block of the longest row since nw_rows / nw_hash
-      // went to four waves per pair and bitop3 rounds (C3: 781 blocks, 5.5 ms)
-      const double est_dev = (maxlen / 128.0) * 0.007 * std::max(1.0, waves / slots);
-      const double est_host = bytes / (350e3 * c->host_threads);
-      devhash = fin_mode == 1 || est_dev < 0.8 * est_host;
-      // nw_align_col under "auto": the device finalize runs after the launch (a
-      // row's SHA-512 is one lane's serial chain: ~4.4 ms for C3's 100 KB rows),
-      // while the streamed host finalize (hstream below) takes each pair as its
-      // walk ends, during the launch -- only the last pair's ~0.3 ms is left
-      // after it.  So host threads finalize wherever they keep up with the fill
-      // (estimated: cells at ~30 TCUPS, or the longest pair's span at ~0.27 us
-      // per step): C3's 8-rank shard 35 -> ~31 ms; C4 (1 GB of rows) stays on
-      // the device.
-      static const int hstream_auto = getenv("NWK_HOST_STREAM") ? atoi(getenv("NWK_HOST_STREAM")) : 1;
-      if (devhash && fin_mode < 0 && pl.mode == kCol && hstream_auto != 0) {
-        double cells = 0, span = 0;
-        for (size_t q = pos; q < end; ++q) {
-          cells += (double)dp[q].m * dp[q].n;
-          span = std::max(span, (double)dp[q].n + 100.0 * (double)ceil_div(dp[q].m, kBitsRows));
-        }
-        const double est_fill = std::max(cells / 3.0e10, span * 0.27e-3);
-        if (est_host < 0.5 * est_fill) devhash = false;
-      }
-      st.device_finalized += devhash ? 1 : 0;
-    }
-    // Layout: [granules | slack | matrices | op strings].  The granule region
-    // always starts at offset 0, so across batches it only ever overlaps
-    // older granules or zeros -- never stale matrix words, whose upper halves
-    // could equal a future epoch tag.  Bytes past the previous batch's
-    // granule region are zeroed before they are used as granules.
-    const int64_t bnd_need_b = bnd * 8 + 4096;  // + slack: band 0's dummy prefetches
-    const int64_t mat_base_b = round_up(bnd_need_b, 256);
-    const int64_t ops_base_b = round_up(mat_base_b + mat * 4, 256);
-    const int64_t segops_base_b = round_up(ops_base_b + ops, 256);
-    // device finalize rows (align1 | align2, op-region layout) + 256 B read slack each
-    const int64_t rows_base_b = round_up(segops_base_b + segops, 256);
-    const int64_t work_b = rows_base_b + 2 * (ops + 256) + 256;  // + slack: traceback tile overrun of the last band
-    void* const old_work = c->d_work.p;
-    if ((rc = c->d_work.ensure((size_t)work_b)) != NWK_OK) return rc;
-    if (c->d_work.p != old_work) c->clean_b = 0;
-    if (bnd_need_b > c->clean_b) {
-      HIP_TRY(hipMemsetAsync(c->d_work.as<uint8_t>() + c->clean_b, 0, (size_t)(bnd_need_b - c->clean_b), c->stream));
-    }
-    c->clean_b = bnd_need_b;
-    // debug: NWK_POISON_BATCH=<byte> fills this batch's matrix region before the
-    // launch, so a walk reading a cell no band of this batch wrote reads that byte
-    // (for nw_align_pka 0x22 is tag 2, a code the fill never writes: the walk fails)
-    static const int poison_batch = getenv("NWK_POISON_BATCH") ? atoi(getenv("NWK_POISON_BATCH")) : -1;
-    if (poison_batch >= 0 && mat > 0)
-      HIP_TRY(hipMemsetAsync(c->d_work.as<uint8_t>() + mat_base_b, poison_batch & 0xff, (size_t)mat * 4, c->stream));
-    // ---- descriptors and dependency-ordered band tasks (band-major)
-    const int par = st.batches & 1;  // host buffer set of this batch
-    if ((rc = c->h_pairs[par].ensure(sizeof(PairDesc) * np)) != NWK_OK) return rc;
-    PairDesc* pd = c->h_pairs[par].as<PairDesc>();
-    int64_t mo = 0, bo = 0, oo = 0, ntasks = 0, so = 0, ro = 0, nsegs = 0, njobs = 0;
-    int maxb = 0;
-    for (int q = 0; q < np; ++q) {
-      const PairWork& w = dp[pos + q];
-      PairDesc& d = pd[q];
-      d.x_off = c->c_off[w.i];
-      d.y_off = c->c_off[w.j];
-      d.e_off = bitsy || gotoh ? c->yw_off[w.j] : c->e_off[w.j];
-      d.xw_off = pl.mode == kBitsStrip ? c->yw_off[w.i] : 0;
-      d.bits_np = pl.mode == kBitsStrip ? strip_np(w.n) : 0;
-      d.prio = 0;
-      d.mat_off = mat_base_b / 4 + mo;
-      d.bnd_off = bo;
-      d.ops_off = ops_base_b + oo;
-      d.m = w.m;
-      d.n = w.n;
-      d.nbands = (int)ceil_div(w.m, bitsy || gotoh ? kBitsRows : kBandRows);
-      d.nchunks = pl.mode == kBitsStrip ? d.bits_np / 64 : gotoh ? (w.n >> 5) + 1 : (int)ceil_div(w.n, 64);
-      d.sblocks = pl.mode == kBits        ? bits_sblocks(d.nchunks)
-                  : pl.mode == kCol       ? col_sblocks(d.nchunks)
-                  : pl.mode == kBitsStrip ? strip_sblocks(w.m, w.n)
-                                          : sblocks_of(pl.mode, d.nchunks);
-      d.bits_w = w.bits_w;
-      d.bits_nblk = w.bits_nblk;
-      d.slot = q;
-      d.spec_every = w.spec;
-      d.nguess = w.nguess;
-      d.task_off = ntasks;  // one tdone entry per task
-      d.seg_off = nsegs;    // nguess seginfo entries per task (kCol: one per band but the last)
-      d.rec_off = ro;
-      d.segops_off = so;
-      if (pl.mode == kCol) {
-        const int64_t nseg = w.spec > 0 ? d.nbands - 1 : 0;
-        nsegs += nseg;
-        ro += nseg * kBitsRows;  // a record per row of each segment's band
-      } else {
-        nsegs += tasks_of(pl.mode, d.nbands) * w.nguess;
-        ro += 32 * (w.m / 128 + 1);
-      }
-      njobs += w.njobs;
-      so += w.segops_b;
-      mo += w.mat_dw; bo += w.bnd_gr; oo += w.ops_b;
-      ntasks += tasks_of(pl.mode, d.nbands);
-      maxb = std::max(maxb, (int)tasks_of(pl.mode, d.nbands));
-    }
-    // kCol, span-bound batches (under two rounds of tasks per wave slot, e.g.
-    // big13): a pair costs at least its span n + ~100 x bands steps, so the
-    // pairs with the longest spans get issue priority over the rest (their
-    // waves then step at nearly a lone wave's rate).  NWK_COL_PRIO=0 disables.
-    static const int col_prio_env = getenv("NWK_COL_PRIO") ? atoi(getenv("NWK_COL_PRIO")) : 1;
-    if (pl.mode == kCol && col_prio_env != 0 && ntasks <= 2 * (int64_t)grid * 4) {
-      double smax = 0;
-      for (int q = 0; q < np; ++q) smax = std::max(smax, (double)pd[q].n + 100.0 * pd[q].nbands);
-      for (int q = 0; q < np; ++q) pd[q].prio = (double)pd[q].n + 100.0 * pd[q].nbands >= 0.7 * smax ? 2 : 0;
-    }
-    // kCol streamed batches (fused finalize: records leave during the launch;
-    // a sharded rank's pairs come in canonical order): the first 1/8 of the
-    // pairs dequeued fill at issue priority 2 and the next 1/8 at 1, so the
-    // lowest canonical ids are out early and rank 0's chain (which consumes
-    // them one record at a time, dist.align_sharded_records) starts on them
-    // while the rest fills.  NWK_PIECE_PRIO=0 disables.
-    static const int piece_prio_env = getenv("NWK_PIECE_PRIO") ? atoi(getenv("NWK_PIECE_PRIO")) : 1;
-    // (want_fuse: the fused finalize below, asked for or automatic)
-    static const int auto_fuse_env = getenv("NWK_AUTO_FUSE") ? atoi(getenv("NWK_AUTO_FUSE")) : 1;
-    const bool want_fuse = devhash && bitsy && !sc.affine &&
-                           (c->opts.finalize == 3 ||
-                            (c->opts.finalize == 0 && auto_fuse_env != 0 && chain && pl.mode == kCol && np >= 8192));
-    // (the first np / div pairs at priority 2, the next np / div at 1; NWK_PIECE_DIV, default 8:
-    // C4 at 8 ranks, chain end 19.85 ms with div 16, 19.05 with 8, 19.63 with 6, profiles/r06/c4_records.txt)
-    // NWK_PIECE_TOP (experiment, default 2): the first tier's priority; each next
-    // np / div pairs one lower, down to 1 (3: the first tier issues level with the walks)
-    static const int piece_div_env = getenv("NWK_PIECE_DIV") ? std::max(2, atoi(getenv("NWK_PIECE_DIV"))) : 8;
-    static const int piece_top_env = getenv("NWK_PIECE_TOP") ? std::min(3, std::max(1, atoi(getenv("NWK_PIECE_TOP")))) : 2;
-    if (pl.mode == kCol && piece_prio_env != 0 && want_fuse && c->opts.finalize == 3 && np >= 32) {
-      const int tier = std::max(1, np / piece_div_env);
-      for (int q = 0; q < np; ++q) {
-        const int pr = piece_top_env - q / tier;
-        if (pr >= 1) pd[q].prio = std::max(pd[q].prio, pr);
-      }
-    }
-    if ((rc = c->h_tasks.ensure(sizeof(int2) * ntasks)) != NWK_OK) return rc;
-    int2* tk = c->h_tasks.as<int2>();
-    // Pair-major (pairs already largest first): a pair's bands are dequeued
-    // together, so pairs finish one after another and each one's traceback
-    // runs concurrently with the fill of the pairs after it.
-    // nw_align_bits with more than one round of tasks per wave slot: band-major.
-    // Its bands trail each other by 2048 + 64 steps, so bands of one pair
-    // dequeued together wait b x 2112 steps; band-major spaces them by a round
-    // of other pairs' bands (C3: 11.5k -> 14.0k GCUPS; C3's 8-rank shard, 1.5
-    // rounds: 59 -> 51 ms; big13, under one round: pair-major 40 vs 44 ms).
-    // NWK_ORDER overrides (0 pair-major, 1 band-major, g >= 2 groups of g
-    // pairs, band-major inside).
-    int64_t t = 0;
-    static const int order_env = getenv("NWK_ORDER") ? atoi(getenv("NWK_ORDER")) : -1;
-    int order = order_env;
-    if (order < 0 && pl.mode == kBits && c->opts.task_order > 0) order = c->opts.task_order == 1 ? 0 : 1;
-    if (order < 0) order = (pl.mode == kBits || pl.mode == kAffinePk || gotoh) && ntasks > 4 * (int64_t)grid ? 1 : 0;
-    if (pl.mode == kBitsStrip) order = 0;  // one task per pair, largest first
-    // kCol: bands trail each other by ~96 steps, so a pair's bands dequeued
-    // together run as one short pipeline: pair-major unless NWK_ORDER says otherwise
-    if (pl.mode == kCol && order_env < 0) order = c->opts.task_order == 2 ? 1 : 0;
-    // kCol paired tasks (nwk_col.hip, two words per lane): one task fills bands
-    // (0,1), (2,3), .. of a pair, an odd last band stays a single.  Off by
-    // default: a paired task issues ~19% fewer scalar instructions per launch
-    // (C3: SQ_INSTS_SALU 5.31e10 -> 4.31e10, VALU 9.18e10 -> 9.26e10), but its
-    // instantiation needs 128 VGPRs (4 waves/SIMD against 5) and C3 measured
-    // 163.3-164.0 ms per step paired against 142.3-142.6 unpaired
-    // (profiles/r07/ab/col_pair.txt).  NWK_COL_PAIR=1 pairs every kCol batch
-    // without the fused finalize (which has no paired instantiation).
-    static const int col_pair_env = getenv("NWK_COL_PAIR") ? atoi(getenv("NWK_COL_PAIR")) : 0;
-    const bool col_pair = pl.mode == kCol && col_pair_env > 0 &&
-                          !(want_fuse && !(getenv("NWK_AFF_NOTRACE") || getenv("NWK_NOTRACE")));
-    // tasks of pair q, and its b-th task's band field
-    auto ntk = [&](int q) -> int {
-      return col_pair ? (pd[q].nbands + 1) / 2 : (int)tasks_of(pl.mode, pd[q].nbands);
-    };
-    auto tke = [&](int q, int b) -> int2 {
-      if (!(col_pair)) return make_int2(q, b);
-      return make_int2(q, 2 * b + 1 < pd[q].nbands ? (2 * b) | kColTaskPair : 2 * b);
-    };
-    if (order == 1) {  // band-major (experiment)
-      for (int b = 0; b < maxb; ++b)
-        for (int q = 0; q < np; ++q)
-          if (b < ntk(q)) tk[t++] = tke(q, b);
-    } else if (order >= 2) {  // groups of `order` pairs, band-major inside a group (experiment)
-      for (int g0 = 0; g0 < np; g0 += order) {
-        const int g1 = std::min(np, g0 + order);
-        int mb = 0;
-        for (int q = g0; q < g1; ++q) mb = std::max(mb, ntk(q));
-        for (int b = 0; b < mb; ++b)
-          for (int q = g0; q < g1; ++q)
-            if (b < ntk(q)) tk[t++] = tke(q, b);
-      }
-    } else {
-      for (int q = 0; q < np; ++q)
-        for (int b = 0; b < ntk(q); ++b) tk[t++] = tke(q, b);
-    }
-    const int64_t ntasks_run = t;  // (< ntasks, the band count, with paired tasks)
-    if ((rc = c->d_pairs.ensure(sizeof(PairDesc) * np)) != NWK_OK) return rc;
-    if ((rc = c->d_tasks.ensure(sizeof(int2) * ntasks)) != NWK_OK) return rc;
-    if ((rc = c->d_oplen.ensure(sizeof(int) * np)) != NWK_OK) return rc;
-    if ((rc = c->d_endij.ensure(sizeof(int2) * np)) != NWK_OK) return rc;
-    if ((rc = c->d_done.ensure(sizeof(unsigned) * np)) != NWK_OK) return rc;
-    if ((rc = c->d_retry.ensure(sizeof(int) * np)) != NWK_OK) return rc;
-    if ((rc = c->h_retry.ensure(sizeof(int) * np)) != NWK_OK) return rc;
-    if ((rc = c->h_oplen[par].ensure(sizeof(int) * np)) != NWK_OK) return rc;
-    if ((rc = c->h_endij[par].ensure(sizeof(int2) * np)) != NWK_OK) return rc;
-    if ((rc = c->h_ops[par].ensure((size_t)ops)) != NWK_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(c->d_pairs.p, pd, sizeof(PairDesc) * np, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_tasks.p, tk, sizeof(int2) * ntasks_run, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_ctl.p, 0, 256, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_done.p, 0, sizeof(unsigned) * np, c->stream));
-    bool windowed = false;
-    for (int q = 0; q < np && !windowed; ++q) windowed = pd[q].bits_w > 0;
-    // fill-vs-walk guard (skel:274): the kernels that give their H(m, n) per
-    // pair (FillArgs::endv); NWK_GUARD=0 disables (A/B)
-    const bool guard = guard_on && guard_mode(pl.mode) && !(getenv("NWK_AFF_NOTRACE") || getenv("NWK_NOTRACE"));
-    if (guard) {
-      st.guard_checked += np;
-      if ((rc = c->d_endv.ensure(sizeof(int) * np)) != NWK_OK) return rc;
-      if ((rc = c->h_endv[par].ensure(sizeof(int) * np)) != NWK_OK) return rc;
-      HIP_TRY(hipMemsetAsync(c->d_endv.p, 0, sizeof(int) * np, c->stream));
-    }
-    if (windowed || guard) HIP_TRY(hipMemsetAsync(c->d_retry.p, 0, sizeof(int) * np, c->stream));
-    // [tdone u32 | seginfo 8 x int | recs u64 | job ready u32 | head, tail | jobs int2]
-    const int64_t seginfo_base_b = ntasks * 4;
-    const int64_t rec_base_b = round_up(seginfo_base_b + nsegs * 32, 8);
-    const int64_t tjr_base_b = rec_base_b + ro * 8;
-    const int64_t tjc_base_b = tjr_base_b + njobs * 4;
-    const int64_t tj_base_b = round_up(tjc_base_b + 8, 8);
-    const int64_t segctl_b = tj_base_b + njobs * 8;
-    if (segmented(pl.mode)) {
-      if ((rc = c->d_segctl.ensure((size_t)segctl_b)) != NWK_OK) return rc;
-      HIP_TRY(hipMemsetAsync(c->d_segctl.p, 0, (size_t)segctl_b, c->stream));
-      c->colseg_clean_b = 0;
-    }
-    // kCol segments: records (u64) in d_segctl, info (int4) in d_colinfo.  A
-    // record counts only with this launch's epoch tag (20 bits), so the record
-    // buffer is cleared only where it may hold anything else: fresh or grown
-    // memory, another mode's data, or once every 2^20 launches (the tag wraps).
-    // The info is cleared per batch (its flag is a whole epoch).
-    const bool colseg = pl.mode == kCol && nsegs > 0;
-    const int64_t colseg_ctl_b = ro * 8;
-    if (colseg) {
-      if ((rc = c->d_colinfo.ensure((size_t)nsegs * 16)) != NWK_OK) return rc;
-      HIP_TRY(hipMemsetAsync(c->d_colinfo.p, 0, (size_t)nsegs * 16, c->stream));
-      void* const old_ctl = c->d_segctl.p;
-      if ((rc = c->d_segctl.ensure((size_t)colseg_ctl_b)) != NWK_OK) return rc;
-      if (c->d_segctl.p != old_ctl || c->epoch + 2u - c->colseg_epoch0 >= (1u << 20)) c->colseg_clean_b = 0;
-      if (c->colseg_clean_b == 0) c->colseg_epoch0 = c->epoch;
-      if (colseg_ctl_b > c->colseg_clean_b) {
-        HIP_TRY(hipMemsetAsync(c->d_segctl.as<uint8_t>() + c->colseg_clean_b, 0, (size_t)(colseg_ctl_b - c->colseg_clean_b),
-                               c->stream));
-        c->colseg_clean_b = colseg_ctl_b;
-      }
-    }
+  // The last member: members are destroyed in reverse order, so on every exit
+  // path ~Joiner joins the finalize thread first, while dp, gl, fused_all and
+  // st above are still alive.  Keep it last.
+  Joiner fin;
+  Job(nwk_ctx* c_, const Scoring& sc_, const Results& res_, std::vector<uint8_t>* a1_, std::vector<uint8_t>* a2_)
+      : c(c_), sc(sc_), res(res_), a1(a1_), a2(a2_) {}
+};
 
-    FillArgs fa{};
-    fa.pairs = c->d_pairs.as<PairDesc>();
-    fa.tasks = c->d_tasks.as<int2>();
-    fa.ntasks = (int)ntasks_run;
-    fa.codes = c->d_codes[pl.kind].as<uint8_t>();
-    fa.E = c->d_E[pl.kind].as<uint32_t>();
-    fa.sel = pl.mode == kPacked    ? c->d_sel[pl.K0 < 0 ? 1 : 0].as<uint32_t>()
-             : band_pairs(pl.mode) ? c->d_sel[2 + (pl.K0 < 0 ? 1 : 0)].as<uint32_t>()
-                                   : nullptr;
-    fa.mat = c->d_work.as<uint32_t>();
-    fa.bnd = c->d_work.as<unsigned long long>();
-    fa.counter = c->d_ctl.as<unsigned>();
-    fa.err = c->d_ctl.as<unsigned>() + 16;
-    fa.done = c->d_done.as<unsigned>();
-    fa.epoch = ++c->epoch;
-    if (fa.epoch == 0) fa.epoch = ++c->epoch;
-    fa.K0 = pl.K0;
-    fa.K1 = pl.K1;
-    fa.go = sc.go;
-    fa.dbg_notrace = (getenv("NWK_AFF_NOTRACE") || getenv("NWK_NOTRACE")) ? 1 : 0;
-    fa.dbg_badwalk = getenv("NWK_DBG_BADWALK") ? atoi(getenv("NWK_DBG_BADWALK")) : 0;
-    static const int band_prio_env = getenv("NWK_BAND_PRIO") ? atoi(getenv("NWK_BAND_PRIO")) : 0;
-    fa.band_prio = band_prio_env;
-    fa.lin_mode = 0;
-    fa.prog = nullptr;
-    fa.yw = bitsy || gotoh ? c->d_yw.as<unsigned>() : nullptr;
-    fa.strip_ring = strip_ring;
-    fa.retry = c->d_retry.as<int>();
-    fa.endv = guard ? c->d_endv.as<int>() : nullptr;
+// Fused finalize: takes each pair's record as its flag arrives (host-mapped,
+// written by the wave that traced the pair) and feeds the chain while the
+// launch still runs.
+struct FusedIn {
+  Results res;
+  int np;
+  const PairWork* dw;  // the batch's pairs
+  std::shared_ptr<FusedSync> sync;
+  unsigned epoch;
+  const unsigned* rflag;  // records: flag [np] | penalty [np] | hash [np][64]
+  const int* rpen;
+  const uint8_t* rhash;
+};
+
+void consume_fused_records(const FusedIn& in) {
+  const int np = in.np;
+  std::vector<char> got((size_t)np, 0);
+  int64_t lo = 0, ngot = 0;
+  for (;;) {
+    const int d = in.sync->done.load(std::memory_order_acquire);
+    if (d == 2) return;
+    bool any = false;
+    const int64_t hi = d ? np : std::min<int64_t>(np, lo + 8192);
+    for (int64_t q = lo; q < hi; ++q) {
+      if (got[(size_t)q] || __atomic_load_n(in.rflag + q, __ATOMIC_ACQUIRE) != in.epoch) continue;
+      in.res.store(in.dw[q].out, in.rpen[q], in.rhash + 64 * q);
+      in.res.publish(in.dw[q].out, true);
+      got[(size_t)q] = 1;
+      ++ngot;
+      any = true;
+    }
+    while (lo < np && got[(size_t)lo]) ++lo;
+    if (in.res.chain && any) in.res.chain->advance();
+    if (d || ngot == np) break;
+    if (!any) std::this_thread::sleep_for(std::chrono::microseconds(20));
+  }
+  // every pair without a record must be a window re-run
+  if (ngot < np) {
+    while (in.sync->done.load(std::memory_order_acquire) == 0) std::this_thread::sleep_for(std::chrono::microseconds(20));
+    if (in.sync->done.load() == 2) return;
+    for (int64_t q = 0; q < np; ++q)
+      if (!got[(size_t)q] && !(!in.sync->skip.empty() && in.sync->skip[(size_t)q])) ++in.sync->missing;
+  }
+}
+
+// Streamed host finalize (nw_align_col): the pair walk writes its moves into
+// host-mapped memory and flags the pair; host threads build rows and hashes
+// while the launch still runs.
+struct StreamIn {
+  Results res;
+  Scoring sc;
+  int np;
+  const PairWork* dw;
+  const PairDesc* pd;  // (h_pairs[par] stays until batch b + 2)
+  std::shared_ptr<FusedSync> sync;
+  unsigned epoch;
+  const int* hrec;      // per slot {flag, length, end i, end j, H(m, n), ..} (kHostRecInts)
+  const uint8_t* hops;  // move strings, op-region layout from ops_base_b
+  int64_t ops_base_b;
+  GuardLog* glog;  // fill-vs-walk guard on: where mismatches go (else nullptr)
+  int64_t gpos;    // dp index of slot 0
+};
+
+void consume_streamed_walks(const StreamIn& in) {
+  const nwk_ctx* c = in.res.c;
+  const int np = in.np;
+  // state per pair: 0 pending, 1 claimed, 2 finalized, 3 left the window (re-run), 4 the
+  // walk failed (length -2: the launch reports the error; the pair is never finalized,
+  // reported or chained), 5 its path's cost is not the fill's H(m, n) (guard: re-run)
+  std::unique_ptr<std::atomic<int>[]> state(new std::atomic<int>[(size_t)np]);
+  for (int64_t q = 0; q < np; ++q) state[q].store(0, std::memory_order_relaxed);
+  std::atomic<int64_t> nleft{np};
+  auto work = [&]() {
+    for (;;) {
+      const int d = in.sync->done.load(std::memory_order_acquire);
+      if (d == 2 || nleft.load(std::memory_order_acquire) == 0) return;
+      bool any = false;
+      for (int64_t q = 0; q < np; ++q) {
+        const int* hr = in.hrec + kHostRecInts * q;
+        if (state[q].load(std::memory_order_relaxed) != 0 || __atomic_load_n(hr, __ATOMIC_ACQUIRE) != (int)in.epoch)
+          continue;
+        int z = 0;
+        if (!state[q].compare_exchange_strong(z, 1)) continue;
+        any = true;
+        const int len = hr[1];
+        if (len < 0) {
+          state[q].store(len == -1 ? 3 : 4, std::memory_order_release);
+        } else {
+          const PairWork& w = in.dw[q];
+          Finalized f;
+          finalize_pair(c->seqs.data() + c->off[w.i], w.m, c->seqs.data() + c->off[w.j], w.n, in.sc,
+                        in.hops + (in.pd[q].ops_off - in.ops_base_b), len, hr[2], hr[3], &f);
+          if (in.glog && f.penalty != hr[4]) {
+            in.glog->add(in.gpos + q, hr[4], f.penalty);
+            state[q].store(5, std::memory_order_release);
+          } else {
+            in.res.store(w.out, f.penalty, f.hash);
+            state[q].store(2, std::memory_order_release);
+          }
+        }
+        nleft.fetch_sub(1, std::memory_order_acq_rel);
+      }
+      if (!any) {
+        if (d == 1) return;  // the launch is over: every flag that will come has come
+        std::this_thread::sleep_for(std::chrono::microseconds(20));
+      }
+    }
+  };
+  std::vector<std::thread> pool;
+  for (int t = 1; t < c->host_threads; ++t) pool.emplace_back(work);
+  // this thread: finalizes too, and reports finished pairs in slot order to the chain
+  std::vector<char> told((size_t)np, 0);
+  int64_t lo = 0;
+  auto report = [&]() {
+    bool any = false;
+    for (int64_t q = lo; q < np; ++q) {
+      if (told[(size_t)q] || state[q].load(std::memory_order_acquire) != 2) continue;
+      in.res.publish(in.dw[q].out, true);
+      told[(size_t)q] = 1;
+      any = true;
+    }
+    while (lo < np && (told[(size_t)lo] || state[lo].load(std::memory_order_acquire) == 3 ||
+                       state[lo].load(std::memory_order_acquire) == 5))
+      ++lo;
+    if (in.res.chain && any) in.res.chain->advance();
+  };
+  std::thread rep_thread;
+  std::atomic<int> stop{0};
+  rep_thread = std::thread([&]() {
+    while (!stop.load(std::memory_order_acquire)) {
+      report();
+      std::this_thread::sleep_for(std::chrono::microseconds(50));
+    }
+    report();
+  });
+  work();
+  for (auto& t : pool) t.join();
+  stop.store(1, std::memory_order_release);
+  rep_thread.join();
+  if (in.sync->done.load() == 2) return;
+  while (in.sync->done.load(std::memory_order_acquire) == 0) std::this_thread::sleep_for(std::chrono::microseconds(20));
+  if (in.sync->done.load() == 2) return;
+  for (int64_t q = 0; q < np; ++q) {
+    const int st_q = state[q].load();
+    const bool skipped = !in.sync->skip.empty() && in.sync->skip[(size_t)q];
+    if ((st_q != 2 && st_q != 5 && !skipped) || (st_q == 2 && skipped)) ++in.sync->missing;
+  }
+}
+
+// Host finalize of a batch after its launch, on the batch's host buffer set
+// (on its own thread while the next batch runs, or inline for the last).
+struct HostFinIn {
+  Results res;
+  Scoring sc;
+  std::vector<uint8_t>* a1;
+  std::vector<uint8_t>* a2;
+  int np;
+  const PairWork* dw;
+  const PairDesc* pd;
+  const int* ol;        // move string lengths
+  const int2* ej;       // walk ends
+  const uint8_t* hops;  // move strings, op-region layout from ops_base_b
+  int64_t ops_base_b;
+  bool devhash;         // penalties and hashes came from the device (hpen, hhash)
+  const int* hpen;
+  const uint8_t* hhash;
+  std::vector<char> skip;  // pairs that re-run (empty: none)
+  const int* hev;          // fill-vs-walk guard on: the fill's H(m, n) per slot (else nullptr)
+  GuardLog* glog;
+  int64_t gpos;            // dp index of slot 0
+};
+
+void finalize_batch_on_host(const HostFinIn& in) {
+  const nwk_ctx* c = in.res.c;
+  const int np = in.np;
+  const PairWork* dw = in.dw;
+  std::vector<char> skip = in.skip;
+  // (guard: pairs whose walked path does not cost the fill's H(m, n) join the skipped ones and re-run)
+  if (in.hev && !in.devhash && skip.empty()) skip.assign((size_t)np, 0);
+  auto skipped = [&](int64_t q) { return !skip.empty() && skip[(size_t)q]; };
+  if (in.devhash) {
+    for (int64_t q = 0; q < np; ++q)
+      if (!skipped(q)) in.res.store(dw[q].out, in.hpen[q], in.hhash + 64 * q);
+  } else parallel_for(in.a1 ? 1 : c->host_threads, np, [&](int64_t q) {
+    if (skipped(q)) return;
+    const PairWork& w = dw[q];
+    Finalized f;
+    finalize_pair(c->seqs.data() + c->off[w.i], w.m, c->seqs.data() + c->off[w.j], w.n, in.sc,
+                  in.hops + (in.pd[q].ops_off - in.ops_base_b), in.ol[q], in.ej[q].x, in.ej[q].y, &f, in.a1, in.a2);
+    if (in.hev && f.penalty != in.hev[q]) {
+      in.glog->add(in.gpos + q, in.hev[q], f.penalty);
+      skip[(size_t)q] = 1;  // (one thread per q: no other writer of this byte)
+      return;
+    }
+    in.res.store(w.out, f.penalty, f.hash);
+  });
+  // Not Results::publish: a whole batch is final at once here, so the pollers
+  // are told first, and the chain schedules (the expensive part) are computed
+  // on all host threads in blocks of 256 pairs before any pair is marked ready.
+  for (int64_t q = 0; q < np; ++q)
+    if (!skipped(q)) mark_ready(in.res.c, dw[q].out);
+  if (Chain* chain = in.res.chain) {  // serial: jobs never overlap each other (fin.join() before the next starts)
+    parallel_for(c->host_threads, (np + 255) / 256, [&](int64_t b) {
+      for (int64_t q = b * 256; q < std::min<int64_t>(np, (b + 1) * 256); ++q)
+        if (!skipped(q)) chain->prepare(dw[q].out);
+    });
+    for (int64_t q = 0; q < np; ++q)
+      if (!skipped(q)) chain->ready[dw[q].out] = 1;
+    chain->advance();
+  }
+}
+
+// ---- one batch: a value, and one function per step (align_work has the order)
+
+struct Batch {
+  size_t pos = 0, end = 0;  // its pairs: dp[pos, end)
+  int np = 0;
+  Footprint sum{};          // of its pairs
+  int par = 0;              // host buffer set (double-buffered: batch b+1 runs while b finalizes)
+  // d_work: [granules | slack | matrices | op strings | segment moves | finalize rows]
+  int64_t bnd_need_b = 0, mat_base_b = 0, ops_base_b = 0, segops_base_b = 0, rows_base_b = 0, work_b = 0;
+  // d_segctl: [tdone u32 | seginfo 8 x int | recs u64 | job ready u32 | head, tail | jobs int2]
+  int64_t seginfo_base_b = 0, rec_base_b = 0, tjr_base_b = 0, tjc_base_b = 0, tj_base_b = 0, segctl_b = 0;
+  int64_t ntasks = 0;      // band (or band-pair) tasks: one tdone entry each
+  int64_t ntasks_run = 0;  // entries of the task list (< ntasks with kCol paired tasks)
+  int64_t nsegs = 0, njobs = 0, nrecs = 0;  // segment infos, queued extra guesses, traceback records
+  bool devhash = false;    // finalize on the device (nw_hash, or fused into the fill launch)
+  bool want_fuse = false;  // the fused finalize applies (fuse unless NWK_NOTRACE)
+  bool fuse = false;       // records stream out of the fill launch (consume_fused_records)
+  bool hstream = false;    // walks stream to the host finalize (consume_streamed_walks)
+  bool guard = false;      // fill-vs-walk guard
+  bool windowed = false;   // some pair stores a window only
+  bool col_pair = false;   // kCol paired tasks
+  bool colseg = false;     // kCol segmented traceback
+  PairDesc* pd = nullptr;  // h_pairs[par]
+  FillArgs fa{};
+  unsigned* rflag = nullptr;  // fuse: host-mapped records {flag [np] | penalty [np] | hash [np][64]}
+  int* rpen = nullptr;
+  uint8_t* rhash = nullptr;
+  double tb0 = 0, tb1 = 0, tb2 = 0;  // host clock: batch formed, copies queued, stream idle
+  float fill_ms = 0;
+  // the consumer thread's hand-off (fuse, hstream).  An early return abandons
+  // the consumer instead of leaving it waiting: a Batch dies before the Job,
+  // so this fires before ~Joiner joins the thread
+  std::shared_ptr<FusedSync> fsync;
+  ~Batch() {
+    int z = 0;
+    if (fsync) fsync->done.compare_exchange_strong(z, 2);
+  }
+};
+
+// Device finalize (nw_hash) when the batch has enough pairs for
+// one lane per row to beat the host threads: est. device ms ~ 0.007 per
+// 128-byte block of the longest row (per wave slot round), host ~ 350 bytes/us
+// per thread.
+void estimate_finalize(Job& job, Batch* b) {
+  const nwk_ctx* c = job.c;
+  const JobPlan& jp = job.plan;
+  const std::vector<PairWork>& dp = jp.dp;
+  b->devhash = false;
+  if (!jp.dev_ok) return;
+  double bytes = 0, maxlen = 0;
+  for (size_t q = b->pos; q < b->end; ++q) {
+    bytes += 2.0 * (dp[q].m + dp[q].n);
+    maxlen = std::max(maxlen, (double)(dp[q].m + dp[q].n));
+  }
+  const double waves = 2.0 * b->np / 64.0, slots = 8.0 * c->cus;
+  // ~0.007 ms per 128-byte block of the longest row since nw_rows / nw_hash
+  // went to four waves per pair and bitop3 rounds (C3: 781 blocks, 5.5 ms)
+  const double est_dev = (maxlen / 128.0) * 0.007 * std::max(1.0, waves / slots);
+  const double est_host = bytes / (350e3 * c->host_threads);
+  b->devhash = jp.fin_mode == 1 || est_dev < 0.8 * est_host;
+  // nw_align_col under "auto": the device finalize runs after the launch (a
+  // row's SHA-512 is one lane's serial chain: ~4.4 ms for C3's 100 KB rows),
+  // while the streamed host finalize (hstream) takes each pair as its
+  // walk ends, during the launch -- only the last pair's ~0.3 ms is left
+  // after it.  So host threads finalize wherever they keep up with the fill
+  // (estimated: cells at ~30 TCUPS, or the longest pair's span at ~0.27 us
+  // per step): C3's 8-rank shard 35 -> ~31 ms; C4 (1 GB of rows) stays on
+  // the device.
+  if (b->devhash && jp.fin_mode < 0 && jp.pl.mode == kCol && knobs().host_stream != 0) {
+    double cells = 0, span = 0;
+    for (size_t q = b->pos; q < b->end; ++q) {
+      cells += (double)dp[q].m * dp[q].n;
+      span = std::max(span, (double)dp[q].n + 100.0 * (double)ceil_div(dp[q].m, kBitsRows));
+    }
+    const double est_fill = std::max(cells / 3.0e10, span * 0.27e-3);
+    if (est_host < 0.5 * est_fill) b->devhash = false;
+  }
+  job.st.device_finalized += b->devhash ? 1 : 0;
+}
+
+// Layout: [granules | slack | matrices | op strings].  The granule region
+// always starts at offset 0, so across batches it only ever overlaps
+// older granules or zeros -- never stale matrix words, whose upper halves
+// could equal a future epoch tag.  Bytes past the previous batch's
+// granule region are zeroed before they are used as granules.
+int layout_work(Job& job, Batch* b) {
+  nwk_ctx* c = job.c;
+  b->bnd_need_b = b->sum.bnd_gr * 8 + 4096;  // + slack: band 0's dummy prefetches
+  b->mat_base_b = round_up(b->bnd_need_b, 256);
+  b->ops_base_b = round_up(b->mat_base_b + b->sum.mat_dw * 4, 256);
+  b->segops_base_b = round_up(b->ops_base_b + b->sum.ops_b, 256);
+  // device finalize rows (align1 | align2, op-region layout) + 256 B read slack each
+  b->rows_base_b = round_up(b->segops_base_b + b->sum.segops_b, 256);
+  b->work_b = b->rows_base_b + 2 * (b->sum.ops_b + 256) + 256;  // + slack: traceback tile overrun of the last band
+  void* const old_work = c->d_work.p;
+  NWK_TRY(c->d_work.ensure((size_t)b->work_b));
+  if (c->d_work.p != old_work) c->clean_b = 0;
+  if (b->bnd_need_b > c->clean_b) {
+    HIP_TRY(hipMemsetAsync(c->d_work.as<uint8_t>() + c->clean_b, 0, (size_t)(b->bnd_need_b - c->clean_b), c->stream));
+  }
+  c->clean_b = b->bnd_need_b;
+  // debug: NWK_POISON_BATCH=<byte> fills this batch's matrix region before the
+  // launch, so a walk reading a cell no band of this batch wrote reads that byte
+  // (for nw_align_pka 0x22 is tag 2, a code the fill never writes: the walk fails)
+  const int poison_batch = knobs().poison_batch;
+  if (poison_batch >= 0 && b->sum.mat_dw > 0)
+    HIP_TRY(hipMemsetAsync(c->d_work.as<uint8_t>() + b->mat_base_b, poison_batch & 0xff, (size_t)b->sum.mat_dw * 4,
+                           c->stream));
+  return NWK_OK;
+}
+
+// Pair descriptors (h_pairs[par]) with the pairs' offsets into both layouts,
+// the batch's task, segment and record counts, and the issue priorities.
+int describe_pairs(Job& job, Batch* b) {
+  nwk_ctx* c = job.c;
+  const JobPlan& jp = job.plan;
+  const Plan& pl = jp.pl;
+  const bool bitsy = jp.bitsy, gotoh = jp.gotoh;
+  const int np = b->np;
+  NWK_TRY(c->h_pairs[b->par].ensure(sizeof(PairDesc) * np));
+  PairDesc* pd = b->pd = c->h_pairs[b->par].as<PairDesc>();
+  int64_t mo = 0, bo = 0, oo = 0, ntasks = 0, so = 0, ro = 0, nsegs = 0, njobs = 0;
+  for (int q = 0; q < np; ++q) {
+    const PairWork& w = jp.dp[b->pos + q];
+    PairDesc& d = pd[q];
+    d.x_off = c->c_off[w.i];
+    d.y_off = c->c_off[w.j];
+    d.e_off = bitsy || gotoh ? c->yw_off[w.j] : c->e_off[w.j];
+    d.xw_off = pl.mode == kBitsStrip ? c->yw_off[w.i] : 0;
+    d.bits_np = pl.mode == kBitsStrip ? strip_np(w.n) : 0;
+    d.prio = 0;
+    d.mat_off = b->mat_base_b / 4 + mo;
+    d.bnd_off = bo;
+    d.ops_off = b->ops_base_b + oo;
+    d.m = w.m;
+    d.n = w.n;
+    d.nbands = (int)ceil_div(w.m, bitsy || gotoh ? kBitsRows : kBandRows);
+    d.nchunks = pl.mode == kBitsStrip ? d.bits_np / 64 : gotoh ? (w.n >> 5) + 1 : (int)ceil_div(w.n, 64);
+    d.sblocks = pl.mode == kBits        ? bits_sblocks(d.nchunks)
+                : pl.mode == kCol       ? col_sblocks(d.nchunks)
+                : pl.mode == kBitsStrip ? strip_sblocks(w.m, w.n)
+                                        : sblocks_of(pl.mode, d.nchunks);
+    d.bits_w = w.bits_w;
+    d.bits_nblk = w.bits_nblk;
+    d.slot = q;
+    d.spec_every = w.spec;
+    d.nguess = w.nguess;
+    d.task_off = ntasks;  // one tdone entry per task
+    d.seg_off = nsegs;    // nguess seginfo entries per task (kCol: one per band but the last)
+    d.rec_off = ro;
+    d.segops_off = so;
+    if (pl.mode == kCol) {
+      const int64_t nseg = w.spec > 0 ? d.nbands - 1 : 0;
+      nsegs += nseg;
+      ro += nseg * kBitsRows;  // a record per row of each segment's band
+    } else {
+      nsegs += tasks_of(pl.mode, d.nbands) * w.nguess;
+      ro += 32 * (w.m / 128 + 1);
+    }
+    njobs += w.njobs;
+    so += w.segops_b;
+    mo += w.mat_dw; bo += w.bnd_gr; oo += w.ops_b;
+    ntasks += tasks_of(pl.mode, d.nbands);
+  }
+  b->ntasks = ntasks;
+  b->nsegs = nsegs;
+  b->njobs = njobs;
+  b->nrecs = ro;
+  // kCol, span-bound batches (under two rounds of tasks per wave slot, e.g.
+  // big13): a pair costs at least its span n + ~100 x bands steps, so the
+  // pairs with the longest spans get issue priority over the rest (their
+  // waves then step at nearly a lone wave's rate).  NWK_COL_PRIO=0 disables.
+  if (pl.mode == kCol && knobs().col_prio != 0 && ntasks <= 2 * (int64_t)jp.grid * 4) {
+    double smax = 0;
+    for (int q = 0; q < np; ++q) smax = std::max(smax, (double)pd[q].n + 100.0 * pd[q].nbands);
+    for (int q = 0; q < np; ++q) pd[q].prio = (double)pd[q].n + 100.0 * pd[q].nbands >= 0.7 * smax ? 2 : 0;
+  }
+  // finalize 3: the bits kernels' device finalize fused into the fill launch
+  // (rows by the tracing wave, SHA-512 by waves that claim 32 traced pairs
+  // from a queue: nwk_bits.hip fin_rows / hq_hash), records streaming to the
+  // host while it runs.  On request (a rank of a sharded job exchanges and
+  // chains finished pairs early); not for nw_align_bits on one GPU, where the
+  // separate nw_rows + nw_hash is faster (C3 161.5 vs 165.4 ms per step).
+  // Automatic for nw_align_col getMinimumPenalties-style calls of >= 8,192
+  // pairs in a batch (C4: 32,640): with the separate finalize the chain's
+  // ~12.5 ms ran after the launch; with records streaming out of it the host
+  // chains while the launch runs.  NWK_AUTO_FUSE=0 disables.
+  b->want_fuse = b->devhash && bitsy && !job.sc.affine &&
+                 (c->opts.finalize == 3 || (c->opts.finalize == 0 && knobs().auto_fuse != 0 && job.res.chain &&
+                                            pl.mode == kCol && np >= 8192));
+  b->fuse = b->want_fuse && !knobs().notrace;
+  // kCol streamed batches (fused finalize: records leave during the launch;
+  // a sharded rank's pairs come in canonical order): the first 1/8 of the
+  // pairs dequeued fill at issue priority 2 and the next 1/8 at 1, so the
+  // lowest canonical ids are out early and rank 0's chain (which consumes
+  // them one record at a time, dist.align_sharded_records) starts on them
+  // while the rest fills.  NWK_PIECE_PRIO=0 disables.
+  // (the first np / div pairs at priority 2, the next np / div at 1; NWK_PIECE_DIV, default 8:
+  // C4 at 8 ranks, chain end 19.85 ms with div 16, 19.05 with 8, 19.63 with 6, profiles/r06/c4_records.txt)
+  // NWK_PIECE_TOP (experiment, default 2): the first tier's priority; each next
+  // np / div pairs one lower, down to 1 (3: the first tier issues level with the walks)
+  if (pl.mode == kCol && knobs().piece_prio != 0 && b->want_fuse && c->opts.finalize == 3 && np >= 32) {
+    const int tier = std::max(1, np / knobs().piece_div);
+    for (int q = 0; q < np; ++q) {
+      const int pr = knobs().piece_top - q / tier;
+      if (pr >= 1) pd[q].prio = std::max(pd[q].prio, pr);
+    }
+  }
+  b->windowed = false;
+  for (int q = 0; q < np && !b->windowed; ++q) b->windowed = pd[q].bits_w > 0;
+  // fill-vs-walk guard (skel:274): the kernels that give their H(m, n) per
+  // pair (FillArgs::endv); NWK_GUARD=0 disables (A/B)
+  b->guard = knobs().guard != 0 && guard_mode(pl.mode) && !knobs().notrace;
+  return NWK_OK;
+}
+
+// The dependency-ordered task list (h_tasks), by order_tasks.
+// Pair-major (pairs already largest first): a pair's bands are dequeued
+// together, so pairs finish one after another and each one's traceback
+// runs concurrently with the fill of the pairs after it.
+// nw_align_bits with more than one round of tasks per wave slot: band-major.
+// Its bands trail each other by 2048 + 64 steps, so bands of one pair
+// dequeued together wait b x 2112 steps; band-major spaces them by a round
+// of other pairs' bands (C3: 11.5k -> 14.0k GCUPS; C3's 8-rank shard, 1.5
+// rounds: 59 -> 51 ms; big13, under one round: pair-major 40 vs 44 ms).
+// NWK_ORDER overrides (0 pair-major, 1 band-major, g >= 2 groups of g
+// pairs, band-major inside).
+int build_tasks(Job& job, Batch* b) {
+  nwk_ctx* c = job.c;
+  const JobPlan& jp = job.plan;
+  const Plan& pl = jp.pl;
+  const int np = b->np;
+  NWK_TRY(c->h_tasks.ensure(sizeof(int2) * b->ntasks));
+  const int order_env = knobs().order;
+  int order = order_env;
+  if (order < 0 && pl.mode == kBits && c->opts.task_order > 0) order = c->opts.task_order == 1 ? 0 : 1;
+  if (order < 0)
+    order = (pl.mode == kBits || pl.mode == kAffinePk || jp.gotoh) && b->ntasks > 4 * (int64_t)jp.grid ? 1 : 0;
+  if (pl.mode == kBitsStrip) order = 0;  // one task per pair, largest first
+  // kCol: bands trail each other by ~96 steps, so a pair's bands dequeued
+  // together run as one short pipeline: pair-major unless NWK_ORDER says otherwise
+  if (pl.mode == kCol && order_env < 0) order = c->opts.task_order == 2 ? 1 : 0;
+  // kCol paired tasks (nwk_col.hip, two words per lane): one task fills bands
+  // (0,1), (2,3), .. of a pair, an odd last band stays a single.  Off by
+  // default: a paired task issues ~19% fewer scalar instructions per launch
+  // (C3: SQ_INSTS_SALU 5.31e10 -> 4.31e10, VALU 9.18e10 -> 9.26e10), but its
+  // instantiation needs 128 VGPRs (4 waves/SIMD against 5) and C3 measured
+  // 163.3-164.0 ms per step paired against 142.3-142.6 unpaired
+  // (profiles/r07/ab/col_pair.txt).  NWK_COL_PAIR=1 pairs every kCol batch
+  // without the fused finalize (which has no paired instantiation).
+  b->col_pair = pl.mode == kCol && knobs().col_pair > 0 && !b->fuse;
+  std::vector<int> nbands((size_t)np), ntk((size_t)np);
+  for (int q = 0; q < np; ++q) {
+    nbands[q] = b->pd[q].nbands;
+    ntk[q] = b->col_pair ? (nbands[q] + 1) / 2 : (int)tasks_of(pl.mode, nbands[q]);
+  }
+  b->ntasks_run = order_tasks(nbands.data(), ntk.data(), np, order, b->col_pair, c->h_tasks.as<int2>());
+  return NWK_OK;
+}
+
+// Device and host buffers of the batch, descriptors and tasks to the device,
+// per-batch clears.  (clean_b / colseg_clean_b: only what may hold anything
+// but zeros or older epochs' tags is cleared.)
+int prepare_buffers(Job& job, Batch* b) {
+  nwk_ctx* c = job.c;
+  const Plan& pl = job.plan.pl;
+  const int np = b->np, par = b->par;
+  NWK_TRY(c->d_pairs.ensure(sizeof(PairDesc) * np));
+  NWK_TRY(c->d_tasks.ensure(sizeof(int2) * b->ntasks));
+  NWK_TRY(c->d_oplen.ensure(sizeof(int) * np));
+  NWK_TRY(c->d_endij.ensure(sizeof(int2) * np));
+  NWK_TRY(c->d_done.ensure(sizeof(unsigned) * np));
+  NWK_TRY(c->d_retry.ensure(sizeof(int) * np));
+  NWK_TRY(c->h_retry.ensure(sizeof(int) * np));
+  NWK_TRY(c->h_oplen[par].ensure(sizeof(int) * np));
+  NWK_TRY(c->h_endij[par].ensure(sizeof(int2) * np));
+  NWK_TRY(c->h_ops[par].ensure((size_t)b->sum.ops_b));
+  HIP_TRY(hipMemcpyAsync(c->d_pairs.p, b->pd, sizeof(PairDesc) * np, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_tasks.p, c->h_tasks.p, sizeof(int2) * b->ntasks_run, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(c->d_ctl.p, 0, 256, c->stream));
+  HIP_TRY(hipMemsetAsync(c->d_done.p, 0, sizeof(unsigned) * np, c->stream));
+  if (b->guard) {
+    job.st.guard_checked += np;
+    NWK_TRY(c->d_endv.ensure(sizeof(int) * np));
+    NWK_TRY(c->h_endv[par].ensure(sizeof(int) * np));
+    HIP_TRY(hipMemsetAsync(c->d_endv.p, 0, sizeof(int) * np, c->stream));
+  }
+  if (b->windowed || b->guard) HIP_TRY(hipMemsetAsync(c->d_retry.p, 0, sizeof(int) * np, c->stream));
+  // [tdone u32 | seginfo 8 x int | recs u64 | job ready u32 | head, tail | jobs int2]
+  b->seginfo_base_b = b->ntasks * 4;
+  b->rec_base_b = round_up(b->seginfo_base_b + b->nsegs * 32, 8);
+  b->tjr_base_b = b->rec_base_b + b->nrecs * 8;
+  b->tjc_base_b = b->tjr_base_b + b->njobs * 4;
+  b->tj_base_b = round_up(b->tjc_base_b + 8, 8);
+  b->segctl_b = b->tj_base_b + b->njobs * 8;
+  if (segmented(pl.mode)) {
+    NWK_TRY(c->d_segctl.ensure((size_t)b->segctl_b));
+    HIP_TRY(hipMemsetAsync(c->d_segctl.p, 0, (size_t)b->segctl_b, c->stream));
+    c->colseg_clean_b = 0;
+  }
+  // kCol segments: records (u64) in d_segctl, info (int4) in d_colinfo.  A
+  // record counts only with this launch's epoch tag (20 bits), so the record
+  // buffer is cleared only where it may hold anything else: fresh or grown
+  // memory, another mode's data, or once every 2^20 launches (the tag wraps).
+  // The info is cleared per batch (its flag is a whole epoch).
+  b->colseg = pl.mode == kCol && b->nsegs > 0;
+  const int64_t colseg_ctl_b = b->nrecs * 8;
+  if (b->colseg) {
+    NWK_TRY(c->d_colinfo.ensure((size_t)b->nsegs * 16));
+    HIP_TRY(hipMemsetAsync(c->d_colinfo.p, 0, (size_t)b->nsegs * 16, c->stream));
+    void* const old_ctl = c->d_segctl.p;
+    NWK_TRY(c->d_segctl.ensure((size_t)colseg_ctl_b));
+    if (c->d_segctl.p != old_ctl || c->epoch + 2u - c->colseg_epoch0 >= (1u << 20)) c->colseg_clean_b = 0;
+    if (c->colseg_clean_b == 0) c->colseg_epoch0 = c->epoch;
+    if (colseg_ctl_b > c->colseg_clean_b) {
+      HIP_TRY(hipMemsetAsync(c->d_segctl.as<uint8_t>() + c->colseg_clean_b, 0, (size_t)(colseg_ctl_b - c->colseg_clean_b),
+                             c->stream));
+      c->colseg_clean_b = colseg_ctl_b;
+    }
+  }
+  return NWK_OK;
+}
+
+// The launch arguments, and the buffers only some finalize paths need.
+int setup_fill_args(Job& job, Batch* b) {
+  nwk_ctx* c = job.c;
+  const JobPlan& jp = job.plan;
+  const Plan& pl = jp.pl;
+  const Scoring& sc = job.sc;
+  const int np = b->np;
+  FillArgs& fa = b->fa;
+  fa.pairs = c->d_pairs.as<PairDesc>();
+  fa.tasks = c->d_tasks.as<int2>();
+  fa.ntasks = (int)b->ntasks_run;
+  fa.codes = c->d_codes[pl.kind].as<uint8_t>();
+  fa.E = c->d_E[pl.kind].as<uint32_t>();
+  fa.sel = pl.mode == kPacked    ? c->d_sel[pl.K0 < 0 ? 1 : 0].as<uint32_t>()
+           : band_pairs(pl.mode) ? c->d_sel[2 + (pl.K0 < 0 ? 1 : 0)].as<uint32_t>()
+                                 : nullptr;
+  fa.mat = c->d_work.as<uint32_t>();
+  fa.bnd = c->d_work.as<unsigned long long>();
+  fa.counter = c->d_ctl.as<unsigned>();
+  fa.err = c->d_ctl.as<unsigned>() + 16;
+  fa.done = c->d_done.as<unsigned>();
+  fa.epoch = ++c->epoch;
+  if (fa.epoch == 0) fa.epoch = ++c->epoch;
+  fa.K0 = pl.K0;
+  fa.K1 = pl.K1;
+  fa.go = sc.go;
+  fa.dbg_notrace = knobs().notrace ? 1 : 0;
+  fa.dbg_badwalk = knobs().dbg_badwalk;
+  fa.band_prio = knobs().band_prio;
+  fa.lin_mode = 0;
+  fa.prog = nullptr;
+  fa.yw = jp.bitsy || jp.gotoh ? c->d_yw.as<unsigned>() : nullptr;
+  fa.strip_ring = jp.strip_ring;
+  fa.retry = c->d_retry.as<int>();
+  fa.endv = b->guard ? c->d_endv.as<int>() : nullptr;
+  fa.pxy = sc.pxy;
+  fa.pgap = sc.pgap;
+  // (tests) NWK_DBG_CORRUPT = slot + 1: the first batch of the call (every batch with
+  // NWK_DBG_CORRUPT_ALL) flips the stored code of cell (m, n) of that pair before its walk
+  fa.dbg_corrupt = job.st.batches == 0 || knobs().dbg_corrupt_all ? knobs().dbg_corrupt : 0;
+  // streamed shards (finalize "fused" asked for): the first two pieces' pairs
+  // (prio >= 1, describe_pairs) are hashed by their tracing wave at once, not in groups
+  // of 32 (the chain on rank 0 waits for the lowest canonical ids).
+  // NWK_EARLY_HASH=0 off, p > 0: prio >= p.
+  fa.early_hash = c->opts.finalize == 3 ? knobs().early_hash : 0;
+  if (knobs().watchdog_set) {
+    NWK_TRY(c->d_prog.ensure(4 * (size_t)(jp.grid + 1) * 4));
+    HIP_TRY(hipMemsetAsync(c->d_prog.p, 0, 4 * (size_t)(jp.grid + 1) * 4, c->stream));
+    fa.prog = c->d_prog.as<unsigned>();
+  }
+  fa.ge = sc.ge;
+  fa.stamps = nullptr;
+  fa.ntasks_pairs = np;
+  if (c->opts.verbose >= 2) {
+    NWK_TRY(c->d_stamps.ensure(88 * (size_t)np + 16 + 16 * (size_t)np));
+    HIP_TRY(hipMemsetAsync(c->d_stamps.as<uint8_t>() + 88 * (size_t)np + 8, 0, 16 * (size_t)np, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_stamps.p, 0, 88 * (size_t)np, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_stamps.as<uint8_t>() + 88 * (size_t)np, 0xff, 8, c->stream));  // kernel start: atomicMin
+    fa.stamps = c->d_stamps.as<unsigned long long>();
+  }
+  fa.ops = c->d_work.as<uint8_t>();
+  const bool seg = segmented(pl.mode);
+  uint8_t* const segctl = c->d_segctl.as<uint8_t>();
+  fa.tdone = seg ? c->d_segctl.as<unsigned>() : nullptr;
+  fa.seginfo = seg ? reinterpret_cast<int*>(segctl + b->seginfo_base_b) : nullptr;
+  fa.recs = seg ? reinterpret_cast<unsigned long long*>(segctl + b->rec_base_b) : nullptr;
+  if (b->colseg) {
+    fa.recs = c->d_segctl.as<unsigned long long>();
+    fa.seginfo = c->d_colinfo.as<int>();
+  }
+  fa.tj_ready = seg ? reinterpret_cast<unsigned*>(segctl + b->tjr_base_b) : nullptr;
+  fa.tj_head = seg ? reinterpret_cast<unsigned*>(segctl + b->tjc_base_b) : nullptr;
+  fa.tj_tail = seg ? fa.tj_head + 1 : nullptr;
+  fa.tjobs = seg ? reinterpret_cast<int2*>(segctl + b->tj_base_b) : nullptr;
+  fa.ntjobs = seg ? (int)b->njobs : 0;
+  fa.segops = c->d_work.as<uint8_t>() + b->segops_base_b;
+  fa.oplen = c->d_oplen.as<int>();
+  fa.endij = c->d_endij.as<int2>();
+  return NWK_OK;
+}
+
+// ... and what the batch's finalize path adds to them: the device finalize's
+// outputs, the fused finalize's records, the streamed host finalize's moves.
+int setup_finalize_args(Job& job, Batch* b) {
+  nwk_ctx* c = job.c;
+  const Scoring& sc = job.sc;
+  const int np = b->np, par = b->par;
+  const int64_t ops = b->sum.ops_b;
+  FillArgs& fa = b->fa;
+  if (b->devhash) {
+    NWK_TRY(c->d_pen.ensure(4 * (size_t)np));
+    NWK_TRY(c->d_hash.ensure(64 * (size_t)np));
+  }
+  if (b->fuse) {  // (want_fuse, describe_pairs)
+    NWK_TRY(c->h_rec[par].ensure((size_t)np * 72, hipHostMallocMapped | hipHostMallocCoherent));
+    b->rflag = c->h_rec[par].as<unsigned>();
+    b->rpen = reinterpret_cast<int*>(b->rflag + np);
+    b->rhash = reinterpret_cast<uint8_t*>(b->rpen + np);
+    fa.fuse_fin = 1;
     fa.pxy = sc.pxy;
     fa.pgap = sc.pgap;
-    // (tests) NWK_DBG_CORRUPT = slot + 1: the first batch of the call (every batch with
-    // NWK_DBG_CORRUPT_ALL) flips the stored code of cell (m, n) of that pair before its walk
-    fa.dbg_corrupt = (st.batches == 0 || getenv("NWK_DBG_CORRUPT_ALL")) && getenv("NWK_DBG_CORRUPT")
-                         ? atoi(getenv("NWK_DBG_CORRUPT")) : 0;
-    // streamed shards (finalize "fused" asked for): the first two pieces' pairs
-    // (prio >= 1 above) are hashed by their tracing wave at once, not in groups
-    // of 32 (the chain on rank 0 waits for the lowest canonical ids).
-    // NWK_EARLY_HASH=0 off, p > 0: prio >= p.
-    static const int early_env = getenv("NWK_EARLY_HASH") ? atoi(getenv("NWK_EARLY_HASH")) : 1;
-    fa.early_hash = c->opts.finalize == 3 ? early_env : 0;
-    if (getenv("NWK_WATCHDOG")) {
-      if ((rc = c->d_prog.ensure(4 * (size_t)(grid + 1) * 4)) != NWK_OK) return rc;
-      HIP_TRY(hipMemsetAsync(c->d_prog.p, 0, 4 * (size_t)(grid + 1) * 4, c->stream));
-      fa.prog = c->d_prog.as<unsigned>();
+    fa.raw = c->d_codes[1].as<uint8_t>();
+    fa.ops_base = b->ops_base_b;
+    fa.rows1 = c->d_work.as<uint8_t>() + b->rows_base_b;
+    fa.rows2 = fa.rows1 + ops + 256;
+    void *dflag = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(&dflag, b->rflag, 0));
+    fa.fin_flag = static_cast<unsigned*>(dflag);
+    fa.fin_pen = reinterpret_cast<int*>(fa.fin_flag + np);
+    fa.fin_hash = reinterpret_cast<uint8_t*>(fa.fin_pen + np);
+    NWK_TRY(c->d_hq.ensure((8 + 8) * (size_t)np));  // queue | row lengths, penalties
+    fa.hq = c->d_hq.as<unsigned long long>();
+    fa.fin_len = reinterpret_cast<int*>(fa.hq + np);
+    fa.hq_ctl = c->d_ctl.as<unsigned>() + 32;  // (d_ctl's 256 bytes are zeroed per batch)
+  }
+  // Streamed host finalize (nw_align_col batches finalized on the host: few
+  // long pairs, big13): the pair walk writes its moves into host-mapped
+  // memory and flags the pair, and host threads build rows and hashes while
+  // the launch still runs -- the pairs traced first (big13: 8 ms into a
+  // 24 ms launch) are done before it ends.  NWK_HOST_STREAM=0 disables.
+  b->hstream = job.plan.pl.mode == kCol && !b->devhash && !b->fuse && job.a1 == nullptr && knobs().host_stream != 0 &&
+               !fa.dbg_notrace;
+  fa.ops_host = nullptr;
+  fa.host_rec = nullptr;
+  if (b->hstream) {
+    NWK_TRY(c->h_opsm[par].ensure((size_t)ops + 256, hipHostMallocMapped | hipHostMallocCoherent));
+    const size_t hrb = sizeof(int) * kHostRecInts * (size_t)np;
+    NWK_TRY(c->h_hrec[par].ensure(hrb, hipHostMallocMapped | hipHostMallocCoherent));
+    memset(c->h_hrec[par].p, 0, hrb);
+    void *dops = nullptr, *drec = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(&dops, c->h_opsm[par].p, 0));
+    HIP_TRY(hipHostGetDevicePointer(&drec, c->h_hrec[par].p, 0));
+    fa.ops_host = static_cast<uint8_t*>(dops);
+    fa.host_rec = static_cast<int*>(drec);
+    fa.ops_base = b->ops_base_b;
+  }
+  return NWK_OK;
+}
+
+// One persistent launch: fill bands, and each pair's traceback runs on the
+// wave that finishes the pair's last band; then the segment gather (kPacked,
+// kPacked2) and the separate device finalize.  Events: ev[0] .. ev[2] the
+// fill launch, ev[2] .. ev[1] what follows it.
+int launch_batch(Job& job, Batch* b) {
+  nwk_ctx* c = job.c;
+  const JobPlan& jp = job.plan;
+  const Plan& pl = jp.pl;
+  const Scoring& sc = job.sc;
+  const FillArgs& fa = b->fa;
+  const int np = b->np, grid = jp.grid;
+  const int64_t ntasks = b->ntasks, ops = b->sum.ops_b;
+  if (c->opts.verbose >= 3) {
+    const std::vector<PairWork>& dp = jp.dp;
+    fprintf(stderr, "nwk batch %d: pairs [%zu, %zu) ids %lld..%lld, %lld tasks, work %.3f GB (mat %.3f, bnd %.3f, ops %.3f)\n",
+            job.st.batches, b->pos, b->end, (long long)dp[b->pos].id, (long long)dp[b->end - 1].id, (long long)ntasks,
+            b->work_b / 1e9, b->sum.mat_dw * 4 / 1e9, b->sum.bnd_gr * 8 / 1e9, ops / 1e9);
+    fflush(stderr);
+  }
+  HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+  if (pl.mode == kBits)
+    HIP_TRY(launch_bits(fa, sc.pxy, sc.pgap, (int)std::min<int64_t>(grid, ceil_div(ntasks, 4)), c->stream));
+  else if (pl.mode == kCol) {
+    // the plain (not fused) instantiation at 5 waves/SIMD (nwk_col.hip
+    // NWK_COL_WPE_HI): C3's 4-rank shard 60.5 -> 48.6 ms; NWK_COL_WPE_HI=0: 4
+    const bool hi = !b->fuse && knobs().col_wpe_hi != 0;
+    const int gcol = col_blocks_per_cu(sc.pgap, hi, b->col_pair) * c->cus;
+    HIP_TRY(launch_col(fa, sc.pxy, sc.pgap, (int)std::min<int64_t>(gcol, ceil_div(b->ntasks_run, 4)), hi, b->col_pair,
+                       c->stream));
+    job.st.col_paired_tasks += (int)(ntasks - b->ntasks_run);  // (each paired task stands for two band tasks)
+  }
+  else if (pl.mode == kBitsStrip)
+    HIP_TRY(launch_strip(fa, sc.pxy, sc.pgap, (int)std::min<int64_t>(grid, ceil_div(ntasks, 4)), c->stream));
+  else if (jp.gotoh)
+    HIP_TRY(launch_gotoh(fa, sc.pxy, sc.go, sc.ge, (int)std::min<int64_t>(grid, ceil_div(ntasks, 4)), c->stream));
+  else
+    HIP_TRY(launch_fill(pl.mode, pl.bits, fa, std::min<int64_t>(grid, ceil_div(ntasks, 4)), c->stream));
+  HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+  if (segmented(pl.mode))
+    HIP_TRY(launch_gather(fa, np, pl.mode == kPacked2 ? 1 : 0, c->stream));  // segment chains -> op strings
+  if (b->devhash && !b->fuse) {
+    HashArgs ha;
+    ha.pairs = fa.pairs;
+    ha.npairs = np;
+    ha.raw = c->d_codes[1].as<uint8_t>();
+    ha.ops = fa.ops;
+    ha.ops_base = b->ops_base_b;
+    ha.rows1 = c->d_work.as<uint8_t>() + b->rows_base_b;
+    ha.rows2 = ha.rows1 + ops + 256;
+    ha.oplen = fa.oplen;
+    ha.endij = fa.endij;
+    ha.pxy = sc.pxy;
+    ha.gopen = sc.affine ? sc.go + sc.ge : sc.pgap;
+    ha.gext = sc.affine ? sc.ge : sc.pgap;
+    ha.penalties = c->d_pen.as<int>();
+    ha.hashes = c->d_hash.as<uint8_t>();
+    ha.endv = fa.endv;
+    ha.retry = fa.retry;
+    HIP_TRY(launch_hash(ha, c->stream));
+  }
+  HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+  return NWK_OK;
+}
+
+// Starts the batch's consumer thread (fuse, hstream) once the one before has ended.
+void start_consumer(Job& job, Batch* b) {
+  nwk_ctx* c = job.c;
+  job.fin.join();
+  b->fsync = std::make_shared<FusedSync>();
+  const PairWork* dw = job.plan.dp.data() + b->pos;  // (dp never reallocates: requeue)
+  if (b->fuse) {
+    const FusedIn in{job.res, b->np, dw, b->fsync, b->fa.epoch, b->rflag, b->rpen, b->rhash};
+    job.fin.start([in]() { consume_fused_records(in); });
+  } else {
+    const StreamIn in{job.res, job.sc, b->np, dw, b->pd, b->fsync, b->fa.epoch, c->h_hrec[b->par].as<int>(),
+                      c->h_opsm[b->par].as<uint8_t>(), b->ops_base_b, b->guard ? &job.gl : nullptr, (int64_t)b->pos};
+    job.fin.start([in]() { consume_streamed_walks(in); });
+  }
+}
+
+// debug (NWK_WATCHDOG=s): report where a launch that does not finish is stuck, then exit
+void watchdog_wait(Job& job, const Batch& b) {
+  nwk_ctx* c = job.c;
+  const int watchdog = knobs().watchdog;
+  if (watchdog <= 0) return;
+  const double t0 = now_ms();
+  while (hipStreamQuery(c->stream) == hipErrorNotReady && now_ms() - t0 < watchdog * 1000.0) usleep(10000);
+  if (hipStreamQuery(c->stream) != hipErrorNotReady) return;
+  std::vector<unsigned> pg(4 * (size_t)(job.plan.grid + 1));
+  hipStream_t s2;
+  (void)hipStreamCreateWithFlags(&s2, hipStreamNonBlocking);
+  (void)hipMemcpyAsync(pg.data(), b.fa.prog, 4 * pg.size(), hipMemcpyDeviceToHost, s2);
+  (void)hipStreamSynchronize(s2);
+  fprintf(stderr, "nwk watchdog: launch still running after %d s; wave markers:\n", watchdog);
+  for (size_t q = 0; q < pg.size(); ++q)
+    if (pg[q]) fprintf(stderr, "  wave %zu: %08x\n", q, pg[q]);
+  fflush(stderr);
+  _exit(3);
+}
+
+// Copies back what the finalize path needs, waits for the stream, reports a
+// hand-off error of the kernels, and books the launch's times.
+int collect_batch(Job& job, Batch* b) {
+  nwk_ctx* c = job.c;
+  const FillArgs& fa = b->fa;
+  const int np = b->np, par = b->par;
+  unsigned herr = 0;
+  HIP_TRY(hipMemcpyAsync(&herr, fa.err, 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->h_oplen[par].p, fa.oplen, sizeof(int) * np, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->h_endij[par].p, fa.endij, sizeof(int2) * np, hipMemcpyDeviceToHost, c->stream));
+  if (b->windowed || b->guard)
+    HIP_TRY(hipMemcpyAsync(c->h_retry.p, fa.retry, sizeof(int) * np, hipMemcpyDeviceToHost, c->stream));
+  if (b->guard) HIP_TRY(hipMemcpyAsync(c->h_endv[par].p, fa.endv, sizeof(int) * np, hipMemcpyDeviceToHost, c->stream));
+  if (b->fuse) {
+    // records arrive in host memory on their own
+  } else if (b->devhash) {  // 68 bytes per pair instead of the move strings
+    NWK_TRY(c->h_pen[par].ensure(4 * (size_t)np));
+    NWK_TRY(c->h_hash[par].ensure(64 * (size_t)np));
+    HIP_TRY(hipMemcpyAsync(c->h_pen[par].p, c->d_pen.p, 4 * (size_t)np, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_hash[par].p, c->d_hash.p, 64 * (size_t)np, hipMemcpyDeviceToHost, c->stream));
+  } else if (!b->hstream) {
+    HIP_TRY(hipMemcpyAsync(c->h_ops[par].p, c->d_work.as<uint8_t>() + b->ops_base_b, (size_t)b->sum.ops_b,
+                           hipMemcpyDeviceToHost, c->stream));
+  }
+  b->tb1 = now_ms();
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  b->tb2 = now_ms();
+  if (herr) {
+    std::vector<unsigned> dn((size_t)np);
+    (void)hipMemcpy(dn.data(), c->d_done.p, sizeof(unsigned) * np, hipMemcpyDeviceToHost);
+    unsigned cnt = 0;
+    (void)hipMemcpy(&cnt, fa.counter, 4, hipMemcpyDeviceToHost);
+    std::vector<int> olv((size_t)np);
+    (void)hipMemcpy(olv.data(), c->d_oplen.p, sizeof(int) * np, hipMemcpyDeviceToHost);
+    std::string d;
+    for (int q = 0; q < np && q < 40; ++q)
+      d += " " + std::to_string(dn[q]) + "/" + std::to_string(b->pd[q].nbands) + ":" + std::to_string(olv[q]);
+    return fail(NWK_EKERNEL, "kernel hand-off timed out (err=%u); dequeued %u of %lld; done%s",
+                herr, cnt, (long long)b->ntasks, d.c_str());
+  }
+  HIP_TRY(hipEventElapsedTime(&b->fill_ms, c->ev[0], c->ev[2]));
+  job.st.fill_ms += b->fill_ms;  // fill + fused traceback (one launch)
+  float ms2 = 0;
+  HIP_TRY(hipEventElapsedTime(&ms2, c->ev[2], c->ev[1]));
+  job.st.traceback_ms += ms2;  // after the fill: segment gather (kPacked2) + device finalize (nw_rows, nw_hash)
+  return NWK_OK;
+}
+
+// verbose >= 2: the segment outcomes of the pairs traced last and every pair's
+// resolved chain (NWK_SEGDUMP); sp: the batch's stamps
+int dump_segments(const Batch& b, int mode, const std::vector<unsigned long long>& sp) {
+  const int np = b.np;
+  const PairDesc* pd = b.pd;
+  std::vector<int> si((size_t)b.nsegs * 8);
+  HIP_TRY(hipMemcpy(si.data(), b.fa.seginfo, si.size() * 4, hipMemcpyDeviceToHost));
+  std::vector<int> ord(np);
+  for (int q = 0; q < np; ++q) ord[q] = q;
+  std::sort(ord.begin(), ord.end(), [&](int x, int y) { return sp[8 * x + 1] > sp[8 * y + 1]; });
+  for (int z = 0; z < std::min(np, 4); ++z) {
+    const int q = ord[z];
+    const int nt = (int)tasks_of(mode, pd[q].nbands);
+    fprintf(stderr, "segments of pair %d (%d x %d, spec every %d):", q, pd[q].m, pd[q].n, pd[q].spec_every);
+    for (int s = 0; s < nt * pd[q].nguess; ++s) {
+      const int* x = &si[8 * ((size_t)pd[q].seg_off + s)];
+      if (x[0] || s == (nt - 1) * pd[q].nguess)
+        fprintf(stderr, " [t%d.%d len %d end (%d,%d) -> %d@%d]", s / pd[q].nguess, s % pd[q].nguess, x[0], x[1], x[2], x[3], x[4]);
     }
-    fa.ge = sc.ge;
-    fa.stamps = nullptr;
-    fa.ntasks_pairs = np;
-    if (c->opts.verbose >= 2) {
-      if ((rc = c->d_stamps.ensure(88 * (size_t)np + 16 + 16 * (size_t)np)) != NWK_OK) return rc;
-      HIP_TRY(hipMemsetAsync(c->d_stamps.as<uint8_t>() + 88 * (size_t)np + 8, 0, 16 * (size_t)np, c->stream));
-      HIP_TRY(hipMemsetAsync(c->d_stamps.p, 0, 88 * (size_t)np, c->stream));
-      HIP_TRY(hipMemsetAsync(c->d_stamps.as<uint8_t>() + 88 * (size_t)np, 0xff, 8, c->stream));  // kernel start: atomicMin
-      fa.stamps = c->d_stamps.as<unsigned long long>();
+    fprintf(stderr, "\n");
+  }
+  for (int q = 0; q < np; ++q) {  // the resolved chain of every pair
+    const int nt = (int)tasks_of(mode, pd[q].nbands), ng = pd[q].nguess;
+    int sgi = (nt - 1) * ng, from = 0;
+    fprintf(stderr, "chain of pair %d:", q);
+    for (int hop = 0; hop < 64; ++hop) {
+      const int* x = &si[8 * ((size_t)pd[q].seg_off + sgi)];
+      fprintf(stderr, " t%d.%d[%d..%d)", sgi / ng, sgi % ng, from, x[0]);
+      if (x[3] < 0) break;
+      from = x[4];
+      sgi = x[3];
     }
-    fa.ops = c->d_work.as<uint8_t>();
-    const bool seg = segmented(pl.mode);
-    fa.tdone = seg ? c->d_segctl.as<unsigned>() : nullptr;
-    fa.seginfo = seg ? reinterpret_cast<int*>(c->d_segctl.as<uint8_t>() + seginfo_base_b) : nullptr;
-    fa.recs = seg ? reinterpret_cast<unsigned long long*>(c->d_segctl.as<uint8_t>() + rec_base_b) : nullptr;
-    if (colseg) {
-      fa.recs = c->d_segctl.as<unsigned long long>();
-      fa.seginfo = c->d_colinfo.as<int>();
+    fprintf(stderr, "\n");
+  }
+  return NWK_OK;
+}
+
+// verbose >= 2: per-pair timeline (100 MHz ticks), relative to the earliest fill-done
+int dump_timeline(const Batch& b, int mode) {
+  const int np = b.np;
+  const PairDesc* pd = b.pd;
+  std::vector<unsigned long long> sp(13 * (size_t)np + 1);
+  HIP_TRY(hipMemcpy(sp.data(), b.fa.stamps, 104 * (size_t)np + 8, hipMemcpyDeviceToHost));
+  unsigned long long t0 = ~0ull, tlast = 0;
+  for (int q = 0; q < np; ++q) t0 = std::min(t0, sp[8 * q]), tlast = std::max(tlast, sp[8 * q]);
+  const unsigned long long tk0 = sp[11 * (size_t)np];
+  fprintf(stderr, "nwk timeline: first pair filled %.3f ms, last pair filled %.3f ms after the kernel's first dequeue\n",
+          (t0 - tk0) / 1e5, (tlast - tk0) / 1e5);
+  if (segmented(mode)) {
+    fprintf(stderr, "nwk timeline: latest segment end per pair (ms after first dequeue; segment task.guess, moves):");
+    for (int q = 0; q < np; ++q) {
+      const unsigned long long te = sp[11 * (size_t)np + 1 + 2 * q], id = sp[11 * (size_t)np + 2 + 2 * q];
+      const int sg = (int)(id >> 32), ng = std::max(1, pd[q].nguess);
+      if (te) fprintf(stderr, " %d:%.2f(t%d.%d,%u)", q, (te - tk0) / 1e5, sg / ng, sg % ng, (unsigned)id);
     }
-    fa.tj_ready = seg ? reinterpret_cast<unsigned*>(c->d_segctl.as<uint8_t>() + tjr_base_b) : nullptr;
-    fa.tj_head = seg ? reinterpret_cast<unsigned*>(c->d_segctl.as<uint8_t>() + tjc_base_b) : nullptr;
-    fa.tj_tail = seg ? fa.tj_head + 1 : nullptr;
-    fa.tjobs = seg ? reinterpret_cast<int2*>(c->d_segctl.as<uint8_t>() + tj_base_b) : nullptr;
-    fa.ntjobs = seg ? (int)njobs : 0;
-    fa.segops = c->d_work.as<uint8_t>() + segops_base_b;
-    fa.oplen = c->d_oplen.as<int>();
-    fa.endij = c->d_endij.as<int2>();
-    // finalize 3: the bits kernels' device finalize fused into the fill launch
-    // (rows by the tracing wave, SHA-512 by waves that claim 32 traced pairs
-    // from a queue: nwk_bits.hip fin_rows / hq_hash), records streaming to the
-    // host while it runs.  On request (a rank of a sharded job exchanges and
-    // chains finished pairs early); not for nw_align_bits on one GPU, where the
-    // separate nw_rows + nw_hash is faster (C3 161.5 vs 165.4 ms per step).
-    // Automatic for nw_align_col getMinimumPenalties-style calls of >= 8,192
-    // pairs in a batch (C4: 32,640): with the separate finalize the chain's
-    // ~12.5 ms ran after the launch; with records streaming out of it the host
-    // chains while the launch runs.  NWK_AUTO_FUSE=0 disables.
-    const bool fuse = want_fuse && !fa.dbg_notrace;
-    if (devhash) {
-      if ((rc = c->d_pen.ensure(4 * (size_t)np)) != NWK_OK) return rc;
-      if ((rc = c->d_hash.ensure(64 * (size_t)np)) != NWK_OK) return rc;
+    fprintf(stderr, "\n");
+  }
+  fprintf(stderr, "nwk timeline (ms after first pair filled; kernel %.3f ms): pair m x n: filled -> traced | "
+                  "trace cycles, runs, moves, tiles/(demand batches << 16 | ahead batches) | fill band-cycles, %% waiting on band above\n", b.fill_ms);
+  double bc = 0, wc = 0;
+  for (int q = 0; q < np; ++q) {
+    const unsigned long long* x = &sp[8 * q];
+    bc += (double)x[6];
+    wc += (double)x[7];
+    fprintf(stderr, "  %3d %6d x %6d: %8.3f -> %8.3f (trace %.3f) | %.3g %.3g %llu %llu/%llu | %.3g %.1f%%\n", q,
+            pd[q].m, pd[q].n, (x[0] - t0) / 1e5, (x[1] - t0) / 1e5, (x[1] - x[0]) / 1e5, (double)x[2], (double)x[3],
+            x[4], x[5] >> 32, x[5] & 0xffffffffull, (double)x[6], x[6] ? 100.0 * (double)x[7] / (double)x[6] : 0.0);
+  }
+  if (segmented(mode) && knobs().segdump) NWK_TRY(dump_segments(b, mode, sp));
+  double w0 = 0, nw = 0, nsb = 0;
+  for (int q = 0; q < np; ++q) {
+    w0 += (double)sp[8 * (size_t)np + 3 * q];
+    nw += (double)sp[8 * (size_t)np + 3 * q + 1];
+    nsb += (double)sp[8 * (size_t)np + 3 * q + 2];
+  }
+  fprintf(stderr, "  all bands: %.4g cycles, %.1f%% waiting on the band above (%.1f%% before the first chunk); "
+                  "%.4g waits over %.4g super-blocks\n",
+          bc, bc > 0 ? 100.0 * wc / bc : 0.0, bc > 0 ? 100.0 * w0 / bc : 0.0, nw, nsb);
+  return NWK_OK;
+}
+
+// A pair re-runs in a later batch: with full storage (windowed storage whose
+// walk left the window, or a walk the fill-vs-walk guard rejected); the
+// affine path has no linear-space fallback, so there it takes the widest
+// doubled window that fits the budget when full storage does not.
+// The only place dp grows after plan_job, and it never grows past its
+// capacity: the finalize threads hold pointers into it.
+int requeue(Job& job, PairWork w) {
+  const nwk_ctx* c = job.c;
+  JobPlan& jp = job.plan;
+  const int old_w = w.bits_w;
+  w.bits_w = 0;
+  set_footprint(jp, job.sc, &w);
+  if ((jp.pl.mode == kAffinePk || jp.gotoh) && w.need() > c->budget) {
+    int nw = 0;
+    for (int64_t cw = 2 * (int64_t)std::max(old_w, 1); cw < (1 << 30); cw *= 2) {
+      PairWork t = w;
+      t.bits_w = (int)cw;
+      set_footprint(jp, job.sc, &t);
+      if (t.need() > c->budget) break;
+      nw = (int)cw;
+      if (t.mat_dw >= w.mat_dw) break;  // as wide as full storage
     }
-    unsigned* rflag = nullptr;
-    int* rpen = nullptr;
-    uint8_t* rhash = nullptr;
-    if (fuse) {
-      const size_t rb = (size_t)np * 72;
-      if ((rc = c->h_rec[par].ensure(rb, hipHostMallocMapped | hipHostMallocCoherent)) != NWK_OK) return rc;
-      rflag = c->h_rec[par].as<unsigned>();
-      rpen = reinterpret_cast<int*>(rflag + np);
-      rhash = reinterpret_cast<uint8_t*>(rpen + np);
+    if (nw == 0)
+      return fail(NWK_ENOMEM, "pair %lld (%d x %d): its traceback left the %d-column storage window and "
+                  "neither full storage (%lld B) nor a %d-column window fits the HBM budget %lld",
+                  (long long)w.id, w.m, w.n, old_w, (long long)w.need(), 2 * old_w, (long long)c->budget);
+    w.bits_w = nw;
+    set_footprint(jp, job.sc, &w);
+  }
+  if (jp.dp.size() == jp.dp.capacity()) return fail(NWK_ENOMEM, "pair %lld: too many re-runs", (long long)w.id);
+  jp.dp.push_back(w);
+  return NWK_OK;
+}
+
+// kBits windowed storage: pairs whose path left the window get no result
+// from this batch; they re-run with full storage in a later batch.  So do the
+// pairs the guard rejected on the device.  skip: 1 per such pair (empty: none).
+int collect_retries(Job& job, const Batch& b, std::vector<char>* skip) {
+  nwk_ctx* c = job.c;
+  if (!(b.windowed || b.guard)) return NWK_OK;
+  const int* rt = c->h_retry.as<int>();
+  for (int q = 0; q < b.np; ++q) {
+    if (!rt[q]) continue;
+    if (skip->empty()) skip->assign((size_t)b.np, 0);
+    (*skip)[q] = 1;
+    PairWork w = job.plan.dp[b.pos + q];
+    if (rt[q] == 2) {  // the guard, on the device (nw_rows / the fused finalize)
+      const int ev = c->h_endv[b.par].as<int>()[q];
+      const int pw = b.devhash && !b.fuse ? c->h_pen[b.par].as<int>()[q] : INT_MIN;  // (fused: on the device only)
+      NWK_TRY(guard_rerun(c, &w, ev, pw, &job.st));
+    } else {
+      job.st.window_retries += 1;
     }
-    if (fuse) {
-      fa.fuse_fin = 1;
-      fa.pxy = sc.pxy;
-      fa.pgap = sc.pgap;
-      fa.raw = c->d_codes[1].as<uint8_t>();
-      fa.ops_base = ops_base_b;
-      fa.rows1 = c->d_work.as<uint8_t>() + rows_base_b;
-      fa.rows2 = fa.rows1 + ops + 256;
-      void *dflag = nullptr;
-      HIP_TRY(hipHostGetDevicePointer(&dflag, rflag, 0));
-      fa.fin_flag = static_cast<unsigned*>(dflag);
-      fa.fin_pen = reinterpret_cast<int*>(fa.fin_flag + np);
-      fa.fin_hash = reinterpret_cast<uint8_t*>(fa.fin_pen + np);
-      if ((rc = c->d_hq.ensure((8 + 8) * (size_t)np)) != NWK_OK) return rc;  // queue | row lengths, penalties
-      fa.hq = c->d_hq.as<unsigned long long>();
-      fa.fin_len = reinterpret_cast<int*>(fa.hq + np);
-      fa.hq_ctl = c->d_ctl.as<unsigned>() + 32;  // (d_ctl's 256 bytes are zeroed per batch)
-    }
-    // Streamed host finalize (nw_align_col batches finalized on the host: few
-    // long pairs, big13): the pair walk writes its moves into host-mapped
-    // memory and flags the pair, and host threads build rows and hashes while
-    // the launch still runs -- the pairs traced first (big13: 8 ms into a
-    // 24 ms launch) are done before it ends.  NWK_HOST_STREAM=0 disables.
-    static const int hstream_env = getenv("NWK_HOST_STREAM") ? atoi(getenv("NWK_HOST_STREAM")) : 1;
-    const bool hstream = pl.mode == kCol && !devhash && !fuse && a1 == nullptr && hstream_env != 0 && !fa.dbg_notrace;
-    fa.ops_host = nullptr;
-    fa.host_rec = nullptr;
-    if (hstream) {
-      if ((rc = c->h_opsm[par].ensure((size_t)ops + 256, hipHostMallocMapped | hipHostMallocCoherent)) != NWK_OK) return rc;
-      const size_t hrb = sizeof(int) * kHostRecInts * (size_t)np;
-      if ((rc = c->h_hrec[par].ensure(hrb, hipHostMallocMapped | hipHostMallocCoherent)) != NWK_OK) return rc;
-      memset(c->h_hrec[par].p, 0, hrb);
-      void *dops = nullptr, *drec = nullptr;
-      HIP_TRY(hipHostGetDevicePointer(&dops, c->h_opsm[par].p, 0));
-      HIP_TRY(hipHostGetDevicePointer(&drec, c->h_hrec[par].p, 0));
-      fa.ops_host = static_cast<uint8_t*>(dops);
-      fa.host_rec = static_cast<int*>(drec);
-      fa.ops_base = ops_base_b;
-    }
-    // One persistent launch: fill bands, and each pair's traceback runs on
-    // the wave that finishes the pair's last band (nw_align).
-    if (c->opts.verbose >= 3) {
-      fprintf(stderr, "nwk batch %d: pairs [%zu, %zu) ids %lld..%lld, %lld tasks, work %.3f GB (mat %.3f, bnd %.3f, ops %.3f)\n",
-              st.batches, pos, end, (long long)dp[pos].id, (long long)dp[end - 1].id, (long long)ntasks, work_b / 1e9,
-              mat * 4 / 1e9, bnd * 8 / 1e9, ops / 1e9);
-      fflush(stderr);
-    }
-    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-    if (pl.mode == kBits)
-      HIP_TRY(launch_bits(fa, sc.pxy, sc.pgap, (int)std::min<int64_t>(grid, ceil_div(ntasks, 4)), c->stream));
-    else if (pl.mode == kCol) {
-      // the plain (not fused) instantiation at 5 waves/SIMD (nwk_col.hip
-      // NWK_COL_WPE_HI): C3's 4-rank shard 60.5 -> 48.6 ms; NWK_COL_WPE_HI=0: 4
-      static const int wpe_hi_env = getenv("NWK_COL_WPE_HI") ? atoi(getenv("NWK_COL_WPE_HI")) : 1;
-      const bool hi = !fuse && wpe_hi_env != 0;
-      const int gcol = col_blocks_per_cu(sc.pgap, hi, col_pair) * c->cus;
-      HIP_TRY(launch_col(fa, sc.pxy, sc.pgap, (int)std::min<int64_t>(gcol, ceil_div(ntasks_run, 4)), hi, col_pair, c->stream));
-      st.col_paired_tasks += (int)(ntasks - ntasks_run);  // (each paired task stands for two band tasks)
-    }
-    else if (pl.mode == kBitsStrip)
-      HIP_TRY(launch_strip(fa, sc.pxy, sc.pgap, (int)std::min<int64_t>(grid, ceil_div(ntasks, 4)), c->stream));
-    else if (gotoh)
-      HIP_TRY(launch_gotoh(fa, sc.pxy, sc.go, sc.ge, (int)std::min<int64_t>(grid, ceil_div(ntasks, 4)), c->stream));
-    else
-      HIP_TRY(launch_fill(pl.mode, pl.bits, fa, std::min<int64_t>(grid, ceil_div(ntasks, 4)), c->stream));
-    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-    if (seg) HIP_TRY(launch_gather(fa, np, pl.mode == kPacked2 ? 1 : 0, c->stream));  // segment chains -> op strings
-    if (devhash && !fuse) {
-      HashArgs ha;
-      ha.pairs = fa.pairs;
-      ha.npairs = np;
-      ha.raw = c->d_codes[1].as<uint8_t>();
-      ha.ops = fa.ops;
-      ha.ops_base = ops_base_b;
-      ha.rows1 = c->d_work.as<uint8_t>() + rows_base_b;
-      ha.rows2 = ha.rows1 + ops + 256;
-      ha.oplen = fa.oplen;
-      ha.endij = fa.endij;
-      ha.pxy = sc.pxy;
-      ha.gopen = sc.affine ? sc.go + sc.ge : sc.pgap;
-      ha.gext = sc.affine ? sc.ge : sc.pgap;
-      ha.penalties = c->d_pen.as<int>();
-      ha.hashes = c->d_hash.as<uint8_t>();
-      ha.endv = fa.endv;
-      ha.retry = fa.retry;
-      HIP_TRY(launch_hash(ha, c->stream));
-    }
-    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    // Fused finalize: a host thread takes each pair's record as its flag
-    // arrives (host-mapped, written by the wave that traced the pair) and
-    // feeds the chain while the launch still runs.
-    std::shared_ptr<FusedSync> fsync;
-    struct FuseGuard {  // an early return abandons the consumer instead of leaving it waiting
-      std::shared_ptr<FusedSync>* f;
-      ~FuseGuard() {
-        int z = 0;
-        if (*f) (*f)->done.compare_exchange_strong(z, 2);
+    NWK_TRY(requeue(job, w));
+  }
+  return NWK_OK;
+}
+
+// Host finalize, overlapped with the next batch's kernel: it runs on its own
+// thread over this batch's host buffer set while the loop goes on to set up,
+// launch and wait for batch b+1 (buffer set par ^ 1); the last batch's inline.
+void finalize_after_launch(Job& job, const Batch& b, std::vector<char> skip, bool last) {
+  nwk_ctx* c = job.c;
+  const int par = b.par;
+  const double tj0 = now_ms();
+  job.fin.join();
+  job.h_join += now_ms() - tj0;
+  const HostFinIn in{job.res, job.sc, job.a1, job.a2, b.np, job.plan.dp.data() + b.pos, b.pd,
+                     c->h_oplen[par].as<int>(), c->h_endij[par].as<int2>(), c->h_ops[par].as<uint8_t>(),
+                     b.ops_base_b, b.devhash, c->h_pen[par].as<int>(), c->h_hash[par].as<uint8_t>(), std::move(skip),
+                     b.guard ? c->h_endv[par].as<int>() : nullptr, &job.gl, (int64_t)b.pos};
+  if (!last) {
+    job.fin.start([in]() { finalize_batch_on_host(in); });
+  } else {
+    const double tf0 = now_ms();
+    finalize_batch_on_host(in);
+    job.h_last += now_ms() - tf0;
+  }
+}
+
+// Linear-space traceback (f2) from pair `pos` on: the pair whose matrix does
+// not fit, alone, with as many bands per group as fit; forced (tests,
+// opts.linear_space = G): as many pairs per linear-space batch as fit.
+int run_linear_batch(Job& job, const BatchCut& cut, bool lin_all, size_t* pos_io) {
+  nwk_ctx* c = job.c;
+  const std::vector<PairWork>& dp = job.plan.dp;
+  const size_t pos = *pos_io;
+  if (c->opts.linear_space < 0 || job.sc.affine)
+    return fail(NWK_ENOMEM, "pair %lld (%d x %d) needs %lld bytes > HBM budget %lld", (long long)dp[pos].id,
+                dp[pos].m, dp[pos].n, (long long)cut.need, (long long)c->budget);
+  job.fin.join();
+  const Plan lpl = lin_plan(job.plan.pl);
+  const int G = lin_all ? c->opts.linear_space : lin_auto_groups(c, lpl, dp[pos]);
+  if (G < 1)
+    return fail(NWK_ENOMEM, "pair (%d x %d): boundary rows and two bands exceed the HBM budget %lld", dp[pos].m,
+                dp[pos].n, (long long)c->budget);
+  size_t lend = pos + 1;
+  int64_t used = lin_geo(lpl, dp[pos], G).bytes;
+  while (lin_all && lend < dp.size()) {
+    const int64_t more = lin_geo(lpl, dp[lend], G).bytes;
+    if (used + more + 8192 > c->budget) break;
+    used += more;
+    ++lend;
+  }
+  const int nl = (int)(lend - pos);
+  std::vector<Finalized> fs((size_t)nl);
+  NWK_TRY(align_linear_batch(c, job.plan.pl, job.sc, dp.data() + pos, nl, G, fs.data(), job.a1, job.a2, &job.st));
+  for (int q = 0; q < nl; ++q) {
+    job.res.store(dp[pos + q].out, fs[q].penalty, fs[q].hash);
+    job.res.publish(dp[pos + q].out, false);
+  }
+  if (job.res.chain) job.res.chain->advance();
+  *pos_io = lend;
+  return NWK_OK;
+}
+
+// Core: aligns `work` (any order) and writes penalties/hashes at work[].out.
+// If a1 != nullptr (single-pair API), also returns the alignment rows.
+// The answer-hash chain of skel:159 advances while later batches still run:
+// results are marked ready by output index (= canonical pair id for a full
+// call) and the chain consumes the ready prefix.
+int align_work(nwk_ctx* c, std::vector<PairWork>& work, const Scoring& sc, int32_t* penalties,
+               uint8_t* hashes, std::vector<uint8_t>* a1, std::vector<uint8_t>* a2, Chain* chain = nullptr) {
+  const double t_start = now_ms();
+  Job job(c, sc, Results{c, penalties, hashes, chain}, a1, a2);
+  NWK_TRY(plan_job(c, work, sc, a1 != nullptr, &job.plan));
+  const JobPlan& jp = job.plan;
+  const Plan& pl = jp.pl;
+  const std::vector<PairWork>& dp = jp.dp;
+  nwk_stats& st = job.st;
+  st.bits = jp.bitsy ? 2 : pl.bits;
+  st.mode = pl.mode;
+  st.window = jp.window;
+  HIP_TRY(hipSetDevice(c->device));
+  // Degenerate pairs (m == 0 or n == 0) have no DP cells: prefix only.
+  for (const auto& w : work) {
+    st.cells += (double)w.m * (double)w.n;
+    if (!(w.m == 0 || w.n == 0)) continue;
+    Finalized f;
+    finalize_pair(c->seqs.data() + c->off[w.i], w.m, c->seqs.data() + c->off[w.j], w.n, sc, nullptr, 0, w.m, w.n, &f,
+                  a1, a2);
+    job.res.store(w.out, f.penalty, f.hash);
+    job.res.publish(w.out, false);
+  }
+  if (!dp.empty()) {
+    NWK_TRY(build_encoding(c, pl.kind));
+    if (jp.bitsy || jp.gotoh) NWK_TRY(build_yw(c));
+    if (pl.mode == kPacked || band_pairs(pl.mode))
+      NWK_TRY(build_sel(c, pl.K0 < 0 ? 1 : 0, band_pairs(pl.mode) ? 64 : 1));
+    if (jp.dev_ok) NWK_TRY(build_encoding(c, 1));
+  }
+  const bool lin_all = c->opts.linear_space > 0 && !sc.affine;  // (tests: every pair through f2)
+  size_t pos = 0;
+  for (;;) {
+    while (pos < dp.size()) {
+      // a batch that fits the HBM budget, or a pair that does not: linear space
+      const BatchCut cut = form_batch(dp.data(), pos, dp.size(), c->budget, lin_all);
+      if (cut.linear) {
+        NWK_TRY(run_linear_batch(job, cut, lin_all, &pos));
+        continue;
       }
-    } fguard{&fsync};
-    if (fuse) {
-      fin.join();
-      fsync = std::make_shared<FusedSync>();
-      const PairWork* dwf = dp.data() + pos;  // (dp never reallocates: reserved for every re-run)
-      const unsigned ep = fa.epoch;
-      fin.start([c, np, dwf, fsync, ep, rflag, rpen, rhash, penalties, hashes, chain]() {
-        std::vector<char> got((size_t)np, 0);
-        int64_t lo = 0, ngot = 0;
-        for (;;) {
-          const int d = fsync->done.load(std::memory_order_acquire);
-          if (d == 2) return;
-          bool any = false;
-          const int64_t hi = d ? np : std::min<int64_t>(np, lo + 8192);
-          for (int64_t q = lo; q < hi; ++q) {
-            if (got[(size_t)q] || __atomic_load_n(rflag + q, __ATOMIC_ACQUIRE) != ep) continue;
-            const PairWork& w = dwf[q];
-            penalties[w.out] = rpen[q];
-            memcpy(hashes + 64 * w.out, rhash + 64 * q, 64);
-            if (chain) {
-              chain->prepare(w.out);
-              chain->ready[w.out] = 1;
-            }
-            mark_ready(c, w.out);
-            got[(size_t)q] = 1;
-            ++ngot;
-            any = true;
-          }
-          while (lo < np && got[(size_t)lo]) ++lo;
-          if (chain && any) chain->advance();
-          if (d || ngot == np) break;
-          if (!any) std::this_thread::sleep_for(std::chrono::microseconds(20));
-        }
-        // every pair without a record must be a window re-run
-        if (ngot < np) {
-          while (fsync->done.load(std::memory_order_acquire) == 0) std::this_thread::sleep_for(std::chrono::microseconds(20));
-          if (fsync->done.load() == 2) return;
-          for (int64_t q = 0; q < np; ++q)
-            if (!got[(size_t)q] && !(!fsync->skip.empty() && fsync->skip[(size_t)q])) ++fsync->missing;
-        }
-      });
-    }
-    if (hstream) {
-      fin.join();
-      fsync = std::make_shared<FusedSync>();
-      const PairWork* dwf = dp.data() + pos;
-      const PairDesc* pdh = pd;  // (h_pairs[par] stays until batch b + 2)
-      const unsigned ep = fa.epoch;
-      const int* hrec = c->h_hrec[par].as<int>();
-      const uint8_t* hops = c->h_opsm[par].as<uint8_t>();
-      const int64_t obase = ops_base_b;
-      GuardLog* glog = &gl;
-      const bool gchk = guard;
-      const int64_t gpos = (int64_t)pos;
-      fin.start([c, np, dwf, pdh, fsync, ep, hrec, hops, obase, sc, penalties, hashes, chain, glog, gchk, gpos]() {
-        // state per pair: 0 pending, 1 claimed, 2 finalized, 3 left the window (re-run), 4 the
-        // walk failed (length -2: the launch reports the error; the pair is never finalized,
-        // reported or chained), 5 its path's cost is not the fill's H(m, n) (guard: re-run)
-        std::unique_ptr<std::atomic<int>[]> state(new std::atomic<int>[(size_t)np]);
-        for (int64_t q = 0; q < np; ++q) state[q].store(0, std::memory_order_relaxed);
-        std::atomic<int64_t> nleft{np};
-        auto work = [&]() {
-          for (;;) {
-            const int d = fsync->done.load(std::memory_order_acquire);
-            if (d == 2 || nleft.load(std::memory_order_acquire) == 0) return;
-            bool any = false;
-            for (int64_t q = 0; q < np; ++q) {
-              const int* hr = hrec + kHostRecInts * q;
-              if (state[q].load(std::memory_order_relaxed) != 0 || __atomic_load_n(hr, __ATOMIC_ACQUIRE) != (int)ep)
-                continue;
-              int z = 0;
-              if (!state[q].compare_exchange_strong(z, 1)) continue;
-              any = true;
-              const int len = hr[1];
-              if (len < 0) {
-                state[q].store(len == -1 ? 3 : 4, std::memory_order_release);
-              } else {
-                const PairWork& w = dwf[q];
-                Finalized f;
-                finalize_pair(c->seqs.data() + c->off[w.i], w.m, c->seqs.data() + c->off[w.j], w.n, sc,
-                              hops + (pdh[q].ops_off - obase), len, hr[2], hr[3], &f);
-                if (gchk && f.penalty != hr[4]) {
-                  glog->add(gpos + q, hr[4], f.penalty);
-                  state[q].store(5, std::memory_order_release);
-                } else {
-                  penalties[w.out] = f.penalty;
-                  memcpy(hashes + 64 * w.out, f.hash, 64);
-                  state[q].store(2, std::memory_order_release);
-                }
-              }
-              nleft.fetch_sub(1, std::memory_order_acq_rel);
-            }
-            if (!any) {
-              if (d == 1) return;  // the launch is over: every flag that will come has come
-              std::this_thread::sleep_for(std::chrono::microseconds(20));
-            }
-          }
-        };
-        std::vector<std::thread> pool;
-        for (int t = 1; t < c->host_threads; ++t) pool.emplace_back(work);
-        // this thread: finalizes too, and reports finished pairs in slot order to the chain
-        std::vector<char> told((size_t)np, 0);
-        int64_t lo = 0;
-        auto report = [&]() {
-          bool any = false;
-          for (int64_t q = lo; q < np; ++q) {
-            if (told[(size_t)q] || state[q].load(std::memory_order_acquire) != 2) continue;
-            const PairWork& w = dwf[q];
-            if (chain) {
-              chain->prepare(w.out);
-              chain->ready[w.out] = 1;
-            }
-            mark_ready(c, w.out);
-            told[(size_t)q] = 1;
-            any = true;
-          }
-          while (lo < np && (told[(size_t)lo] || state[lo].load(std::memory_order_acquire) == 3 ||
-                             state[lo].load(std::memory_order_acquire) == 5))
-            ++lo;
-          if (chain && any) chain->advance();
-        };
-        std::thread rep_thread;
-        std::atomic<int> stop{0};
-        rep_thread = std::thread([&]() {
-          while (!stop.load(std::memory_order_acquire)) {
-            report();
-            std::this_thread::sleep_for(std::chrono::microseconds(50));
-          }
-          report();
-        });
-        work();
-        for (auto& t : pool) t.join();
-        stop.store(1, std::memory_order_release);
-        rep_thread.join();
-        if (fsync->done.load() == 2) return;
-        while (fsync->done.load(std::memory_order_acquire) == 0) std::this_thread::sleep_for(std::chrono::microseconds(20));
-        if (fsync->done.load() == 2) return;
-        for (int64_t q = 0; q < np; ++q) {
-          const int st_q = state[q].load();
-          const bool skipped = !fsync->skip.empty() && fsync->skip[(size_t)q];
-          if ((st_q != 2 && st_q != 5 && !skipped) || (st_q == 2 && skipped)) ++fsync->missing;
-        }
-      });
-    }
-    if (c->opts.verbose >= 3) {
-      fprintf(stderr, "nwk batch %d: launched mode %d bits %d grid %d, waiting\n", st.batches, pl.mode, pl.bits, grid);
-      fflush(stderr);
-    }
-    static const int watchdog = getenv("NWK_WATCHDOG") ? atoi(getenv("NWK_WATCHDOG")) : 0;
-    if (watchdog > 0) {  // debug: report where a launch that does not finish is stuck, then exit
-      const double t0 = now_ms();
-      while (hipStreamQuery(c->stream) == hipErrorNotReady && now_ms() - t0 < watchdog * 1000.0) usleep(10000);
-      if (hipStreamQuery(c->stream) == hipErrorNotReady) {
-        std::vector<unsigned> pg(4 * (size_t)(grid + 1));
-        hipStream_t s2;
-        (void)hipStreamCreateWithFlags(&s2, hipStreamNonBlocking);
-        (void)hipMemcpyAsync(pg.data(), fa.prog, 4 * pg.size(), hipMemcpyDeviceToHost, s2);
-        (void)hipStreamSynchronize(s2);
-        fprintf(stderr, "nwk watchdog: launch still running after %d s; wave markers:\n", watchdog);
-        for (size_t q = 0; q < pg.size(); ++q)
-          if (pg[q]) fprintf(stderr, "  wave %zu: %08x\n", q, pg[q]);
+      Batch b;
+      b.pos = pos;
+      b.end = cut.end;
+      b.np = (int)(cut.end - pos);
+      b.sum = cut.sum;
+      b.par = st.batches & 1;
+      b.tb0 = now_ms();
+      estimate_finalize(job, &b);
+      NWK_TRY(layout_work(job, &b));
+      NWK_TRY(describe_pairs(job, &b));
+      NWK_TRY(build_tasks(job, &b));
+      NWK_TRY(prepare_buffers(job, &b));
+      NWK_TRY(setup_fill_args(job, &b));
+      NWK_TRY(setup_finalize_args(job, &b));
+      NWK_TRY(launch_batch(job, &b));
+      if (b.fuse || b.hstream) start_consumer(job, &b);
+      if (c->opts.verbose >= 3) {
+        fprintf(stderr, "nwk batch %d: launched mode %d bits %d grid %d, waiting\n", st.batches, pl.mode, pl.bits, jp.grid);
         fflush(stderr);
-        _exit(3);
       }
-    }
-    unsigned herr = 0;
-    HIP_TRY(hipMemcpyAsync(&herr, fa.err, 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->h_oplen[par].p, fa.oplen, sizeof(int) * np, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->h_endij[par].p, fa.endij, sizeof(int2) * np, hipMemcpyDeviceToHost, c->stream));
-    if (windowed || guard)
-      HIP_TRY(hipMemcpyAsync(c->h_retry.p, fa.retry, sizeof(int) * np, hipMemcpyDeviceToHost, c->stream));
-    if (guard) HIP_TRY(hipMemcpyAsync(c->h_endv[par].p, fa.endv, sizeof(int) * np, hipMemcpyDeviceToHost, c->stream));
-    if (fuse) {
-      // records arrive in host memory on their own
-    } else if (devhash) {  // 68 bytes per pair instead of the move strings
-      if ((rc = c->h_pen[par].ensure(4 * (size_t)np)) != NWK_OK) return rc;
-      if ((rc = c->h_hash[par].ensure(64 * (size_t)np)) != NWK_OK) return rc;
-      HIP_TRY(hipMemcpyAsync(c->h_pen[par].p, c->d_pen.p, 4 * (size_t)np, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipMemcpyAsync(c->h_hash[par].p, c->d_hash.p, 64 * (size_t)np, hipMemcpyDeviceToHost, c->stream));
-    } else if (!hstream) {
-      HIP_TRY(hipMemcpyAsync(c->h_ops[par].p, c->d_work.as<uint8_t>() + ops_base_b, (size_t)ops,
-                             hipMemcpyDeviceToHost, c->stream));
-    }
-    const double tb1 = now_ms();
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const double tb2 = now_ms();
-    if (herr) {
-      std::vector<unsigned> dn((size_t)np);
-      (void)hipMemcpy(dn.data(), c->d_done.p, sizeof(unsigned) * np, hipMemcpyDeviceToHost);
-      unsigned cnt = 0;
-      (void)hipMemcpy(&cnt, fa.counter, 4, hipMemcpyDeviceToHost);
-      std::vector<int> olv((size_t)np);
-      (void)hipMemcpy(olv.data(), c->d_oplen.p, sizeof(int) * np, hipMemcpyDeviceToHost);
-      std::string d;
-      for (int q = 0; q < np && q < 40; ++q)
-        d += " " + std::to_string(dn[q]) + "/" + std::to_string(pd[q].nbands) + ":" + std::to_string(olv[q]);
-      return fail(NWK_EKERNEL, "kernel hand-off timed out (err=%u); dequeued %u of %lld; done%s",
-                  herr, cnt, (long long)ntasks, d.c_str());
-    }
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[2]));
-    st.fill_ms += ms;  // fill + fused traceback (one launch)
-    float ms2 = 0;
-    HIP_TRY(hipEventElapsedTime(&ms2, c->ev[2], c->ev[1]));
-    st.traceback_ms += ms2;  // after the fill: segment gather (kPacked2) + device finalize (nw_rows, nw_hash)
-    if (fa.stamps) {  // per-pair timeline (100 MHz ticks), relative to the earliest fill-done
-      std::vector<unsigned long long> sp(13 * (size_t)np + 1);
-      HIP_TRY(hipMemcpy(sp.data(), fa.stamps, 104 * (size_t)np + 8, hipMemcpyDeviceToHost));
-      unsigned long long t0 = ~0ull, tlast = 0;
-      for (int q = 0; q < np; ++q) t0 = std::min(t0, sp[8 * q]), tlast = std::max(tlast, sp[8 * q]);
-      const unsigned long long tk0 = sp[11 * (size_t)np];
-      fprintf(stderr, "nwk timeline: first pair filled %.3f ms, last pair filled %.3f ms after the kernel's first dequeue\n",
-              (t0 - tk0) / 1e5, (tlast - tk0) / 1e5);
-      if (segmented(pl.mode)) {
-        fprintf(stderr, "nwk timeline: latest segment end per pair (ms after first dequeue; segment task.guess, moves):");
-        for (int q = 0; q < np; ++q) {
-          const unsigned long long te = sp[11 * (size_t)np + 1 + 2 * q], id = sp[11 * (size_t)np + 2 + 2 * q];
-          const int sg = (int)(id >> 32), ng = std::max(1, pd[q].nguess);
-          if (te) fprintf(stderr, " %d:%.2f(t%d.%d,%u)", q, (te - tk0) / 1e5, sg / ng, sg % ng, (unsigned)id);
+      watchdog_wait(job, b);
+      NWK_TRY(collect_batch(job, &b));
+      if (b.fa.stamps) NWK_TRY(dump_timeline(b, pl.mode));
+      st.matrix_bytes += b.sum.mat_dw * 4;
+      st.batches += 1;
+      st.fill_launches += 1;
+      std::vector<char> skip;
+      NWK_TRY(collect_retries(job, b, &skip));
+      const bool last = b.end >= dp.size();  // (after the re-runs were appended)
+      if (b.fuse || b.hstream) {  // the consumer finishes on its own; the next join collects it
+        b.fsync->skip = skip;
+        b.fsync->done.store(1, std::memory_order_release);
+        job.fused_all.push_back(b.fsync);
+        if (last) {
+          const double tf0 = now_ms();
+          job.fin.join();
+          job.h_last += now_ms() - tf0;
         }
-        fprintf(stderr, "\n");
+      } else {
+        finalize_after_launch(job, b, std::move(skip), last);
       }
-      fprintf(stderr, "nwk timeline (ms after first pair filled; kernel %.3f ms): pair m x n: filled -> traced | "
-                      "trace cycles, runs, moves, tiles/(demand batches << 16 | ahead batches) | fill band-cycles, %% waiting on band above\n", ms);
-      double bc = 0, wc = 0;
-      for (int q = 0; q < np; ++q) {
-        const unsigned long long* x = &sp[8 * q];
-        bc += (double)x[6];
-        wc += (double)x[7];
-        fprintf(stderr, "  %3d %6d x %6d: %8.3f -> %8.3f (trace %.3f) | %.3g %.3g %llu %llu/%llu | %.3g %.1f%%\n", q,
-                pd[q].m, pd[q].n, (x[0] - t0) / 1e5, (x[1] - t0) / 1e5, (x[1] - x[0]) / 1e5, (double)x[2], (double)x[3],
-                x[4], x[5] >> 32, x[5] & 0xffffffffull, (double)x[6], x[6] ? 100.0 * (double)x[7] / (double)x[6] : 0.0);
-      }
-      if (segmented(pl.mode) && getenv("NWK_SEGDUMP")) {  // segment outcomes of the pairs traced last
-        std::vector<int> si((size_t)nsegs * 8);
-        HIP_TRY(hipMemcpy(si.data(), fa.seginfo, si.size() * 4, hipMemcpyDeviceToHost));
-        std::vector<int> ord(np);
-        for (int q = 0; q < np; ++q) ord[q] = q;
-        std::sort(ord.begin(), ord.end(), [&](int x, int y) { return sp[8 * x + 1] > sp[8 * y + 1]; });
-        for (int z = 0; z < std::min(np, 4); ++z) {
-          const int q = ord[z];
-          const int nt = (int)tasks_of(pl.mode, pd[q].nbands);
-          fprintf(stderr, "segments of pair %d (%d x %d, spec every %d):", q, pd[q].m, pd[q].n, pd[q].spec_every);
-          for (int b = 0; b < nt * pd[q].nguess; ++b) {
-            const int* x = &si[8 * ((size_t)pd[q].seg_off + b)];
-            if (x[0] || b == (nt - 1) * pd[q].nguess)
-              fprintf(stderr, " [t%d.%d len %d end (%d,%d) -> %d@%d]", b / pd[q].nguess, b % pd[q].nguess, x[0], x[1], x[2], x[3], x[4]);
-          }
-          fprintf(stderr, "\n");
-        }
-        for (int q = 0; q < np; ++q) {  // the resolved chain of every pair
-          const int nt = (int)tasks_of(pl.mode, pd[q].nbands), ng = pd[q].nguess;
-          int sgi = (nt - 1) * ng, from = 0;
-          fprintf(stderr, "chain of pair %d:", q);
-          for (int hop = 0; hop < 64; ++hop) {
-            const int* x = &si[8 * ((size_t)pd[q].seg_off + sgi)];
-            fprintf(stderr, " t%d.%d[%d..%d)", sgi / ng, sgi % ng, from, x[0]);
-            if (x[3] < 0) break;
-            from = x[4];
-            sgi = x[3];
-          }
-          fprintf(stderr, "\n");
-        }
-      }
-      double w0 = 0, nw = 0, nsb = 0;
-      for (int q = 0; q < np; ++q) {
-        w0 += (double)sp[8 * (size_t)np + 3 * q];
-        nw += (double)sp[8 * (size_t)np + 3 * q + 1];
-        nsb += (double)sp[8 * (size_t)np + 3 * q + 2];
-      }
-      fprintf(stderr, "  all bands: %.4g cycles, %.1f%% waiting on the band above (%.1f%% before the first chunk); "
-                      "%.4g waits over %.4g super-blocks\n",
-              bc, bc > 0 ? 100.0 * wc / bc : 0.0, bc > 0 ? 100.0 * w0 / bc : 0.0, nw, nsb);
+      job.h_setup += b.tb1 - b.tb0;
+      job.h_sync += b.tb2 - b.tb1;
+      pos = b.end;
     }
-    st.matrix_bytes += mat * 4;
-    st.batches += 1;
-    st.fill_launches += 1;
-    // kBits windowed storage: pairs whose path left the window get no result
-    // from this batch; they re-run with full storage in a later batch
-    std::vector<char> skip;
-    if (windowed || guard) {
-      const int* rt = c->h_retry.as<int>();
-      for (int q = 0; q < np; ++q) {
-        if (!rt[q]) continue;
-        if (skip.empty()) skip.assign((size_t)np, 0);
-        skip[q] = 1;
-        PairWork w = dp[pos + q];
-        if (rt[q] == 2) {  // the guard, on the device (nw_rows / the fused finalize)
-          const int ev = c->h_endv[par].as<int>()[q];
-          const int pw = devhash && !fuse ? c->h_pen[par].as<int>()[q] : INT_MIN;  // (fused: on the device only)
-          if ((rc = guard_rerun(c, &w, ev, pw, &st)) != NWK_OK) return rc;
-        } else {
-          st.window_retries += 1;
-        }
-        if ((rc = requeue(w)) != NWK_OK) return rc;
-      }
+    job.fin.join();
+    // pairs the host finalize rejected (fill-vs-walk guard) re-run in new batches
+    const auto gbad = job.gl.take();
+    if (gbad.empty()) break;
+    for (const auto& g : gbad) {
+      PairWork w = dp[(size_t)g.idx];
+      NWK_TRY(guard_rerun(c, &w, g.endv, g.cost, &st));
+      NWK_TRY(requeue(job, w));
     }
-    if (fuse || hstream) {  // the consumer finishes on its own; the next join collects it
-      fsync->skip = skip;
-      fsync->done.store(1, std::memory_order_release);
-      h_setup += tb1 - tb0;
-      h_sync += tb2 - tb1;
-      fused_all.push_back(fsync);
-      if (end >= dp.size()) {
-        const double tf0 = now_ms();
-        fin.join();
-        h_last += now_ms() - tf0;
-      }
-      pos = end;
-      continue;
-    }
-    // ---- host finalize, overlapped with the next batch's kernel: it runs on
-    // its own thread over this batch's host buffer set while the loop goes
-    // on to set up, launch and wait for batch b+1 (buffer set par ^ 1).
-    const double tj0 = now_ms();
-    fin.join();
-    h_join += now_ms() - tj0;
-    const int* ol = c->h_oplen[par].as<int>();
-    const int2* ej = c->h_endij[par].as<int2>();
-    const uint8_t* hops = c->h_ops[par].as<uint8_t>();
-    const PairWork* dw = dp.data() + pos;
-    const int* hpen = c->h_pen[par].as<int>();
-    const uint8_t* hhash = c->h_hash[par].as<uint8_t>();
-    const int* hev = guard ? c->h_endv[par].as<int>() : nullptr;  // the fill's H(m, n) per slot
-    GuardLog* glog = &gl;
-    const int64_t gpos = (int64_t)pos;
-    auto job = [c, a1, a2, np, dw, pd, ol, ej, hops, ops_base_b, sc, penalties, hashes, chain, devhash, hpen, hhash,
-                skip, hev, glog, gpos]() mutable {
-      // (guard: pairs whose walked path does not cost the fill's H(m, n) join the skipped ones and re-run)
-      if (hev && !devhash && skip.empty()) skip.assign((size_t)np, 0);
-      auto skipped = [&](int64_t q) { return !skip.empty() && skip[(size_t)q]; };
-      if (devhash) {
-        for (int64_t q = 0; q < np; ++q) {
-          if (skipped(q)) continue;
-          penalties[dw[q].out] = hpen[q];
-          memcpy(hashes + 64 * dw[q].out, hhash + 64 * q, 64);
-        }
-      } else parallel_for(a1 ? 1 : c->host_threads, np, [&](int64_t q) {
-        if (skipped(q)) return;
-        const PairWork& w = dw[q];
-        const PairDesc& d = pd[q];
-        Finalized f;
-        finalize_pair(c->seqs.data() + c->off[w.i], w.m, c->seqs.data() + c->off[w.j], w.n, sc,
-                      hops + (d.ops_off - ops_base_b), ol[q], ej[q].x, ej[q].y, &f, a1, a2);
-        if (hev && f.penalty != hev[q]) {
-          glog->add(gpos + q, hev[q], f.penalty);
-          skip[(size_t)q] = 1;  // (one thread per q: no other writer of this byte)
-          return;
-        }
-        penalties[w.out] = f.penalty;
-        memcpy(hashes + 64 * w.out, f.hash, 64);
-      });
-      for (int64_t q = 0; q < np; ++q)
-        if (!skipped(q)) mark_ready(c, dw[q].out);
-      if (chain) {  // serial: jobs never overlap each other (fin.join() before the next starts)
-        parallel_for(c->host_threads, (np + 255) / 256, [&](int64_t b) {  // second-block schedules, in parallel
-          for (int64_t q = b * 256; q < std::min<int64_t>(np, (b + 1) * 256); ++q)
-            if (!skipped(q)) chain->prepare(dw[q].out);
-        });
-        for (int64_t q = 0; q < np; ++q)
-          if (!skipped(q)) chain->ready[dw[q].out] = 1;
-        chain->advance();
-      }
-    };
-    if (end < dp.size()) fin.start(job);
-    else { const double tf0 = now_ms(); job(); h_last += now_ms() - tf0; }
-    h_setup += tb1 - tb0;
-    h_sync += tb2 - tb1;
-    pos = end;
   }
-  fin.join();
-  // pairs the host finalize rejected (fill-vs-walk guard) re-run in new batches
-  const auto gbad = gl.take();
-  if (gbad.empty()) break;
-  for (const auto& g : gbad) {
-    PairWork w = dp[(size_t)g.idx];
-    if ((rc = guard_rerun(c, &w, g.endv, g.cost, &st)) != NWK_OK) return rc;
-    if ((rc = requeue(w)) != NWK_OK) return rc;
-  }
-  }
-  for (const auto& f : fused_all)
+  for (const auto& f : job.fused_all)
     if (f->missing) return fail(NWK_EKERNEL, "fused finalize: %lld pair(s) without a record", (long long)f->missing);
   st.total_ms = now_ms() - t_start;
   if (c->opts.verbose)
-    fprintf(stderr, "nwk host: setup+launch %.3f ms, kernel+copies wait %.3f ms, finalize join %.3f ms, last finalize %.3f ms\n", h_setup, h_sync, h_join, h_last);
+    fprintf(stderr, "nwk host: setup+launch %.3f ms, kernel+copies wait %.3f ms, finalize join %.3f ms, last finalize %.3f ms\n",
+            job.h_setup, job.h_sync, job.h_join, job.h_last);
   c->stats = st;
   if (c->opts.verbose)
     fprintf(stderr, "nwk: %zu pairs, %.3g cells, fill %.3f ms (%.1f GCUPS), traceback %.3f ms, total %.3f ms, bits %d mode %d, %d batch(es), window %d, %d retries\n",
@@ -2393,6 +2690,7 @@ int align_work(nwk_ctx* c, std::vector<PairWork>& work, const Scoring& sc, int32
             st.traceback_ms, st.total_ms, st.bits, st.mode, st.batches, dp.empty() ? 0 : dp[0].bits_w, (int)st.window_retries);
   return NWK_OK;
 }
+
 
 int make_work(const nwk_ctx* c, const int64_t* ids, int64_t n, std::vector<PairWork>* out) {
   const int64_t P = (int64_t)c->k * (c->k - 1) / 2;

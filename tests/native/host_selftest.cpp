@@ -5,20 +5,24 @@
 // a fixture the test writes from the golden vectors.  Needs no GPU: it covers the
 // SHA-512, the answer-hash chain (skel:155-159), the host finalize of traced moves
 // (skel:263-272, 135-157), the LPT shard, argument checking and the no-device error
-// path.  Fixture lines (fields separated by one space, "-" = empty):
+// path, and (without a fixture line) the batch scheduler's pure parts, order_tasks and
+// form_batch of nwk_sched.h.  Fixture lines (fields separated by one space, "-" = empty):
 //   sha   <data hex> <sha512 hex>
 //   chain <P> <answer hex> <problemhash hex> x P
 //   fin   <x> <y> <pxy> <pgap> <moves> <penalty> <align1> <align2> <problemhash hex>
 //   shard <world> <L_0> ... <L_{k-1}>
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
 #include <sstream>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/nwk.h"
+#include "../../multiple-sequence-alignment-openmp-openmpi_amd/csrc/nwk_sched.h"
 
 static int failures = 0;
 #define CHECK(cond, ...)                              \
@@ -153,7 +157,104 @@ static void check_args() {
   }
 }
 
+// order_tasks (nwk_sched.h): a band that is missing, duplicated or out of order
+// hangs a persistent kernel, so every list is checked entry by entry.
+static void check_task_list(const std::vector<int>& nbands, int order, bool paired, bool band_pairs) {
+  const int np = (int)nbands.size();
+  std::vector<int> ntk(nbands.size());
+  int64_t want = 0;
+  for (int q = 0; q < np; ++q) want += ntk[q] = paired || band_pairs ? (nbands[q] + 1) / 2 : nbands[q];
+  std::vector<int2> tk((size_t)want + 8, make_int2(-1, -1));
+  const int64_t got = nwk::order_tasks(nbands.data(), ntk.data(), np, order, paired, tk.data());
+  CHECK(got == want, "order %d paired %d: %lld entries, want %lld", order, (int)paired, (long long)got, (long long)want);
+  CHECK(tk[(size_t)want].x == -1, "order %d: wrote past the list", order);
+  // (unpaired lists count tasks: bands, or band pairs whose band field is the task index)
+  std::vector<std::vector<int>> seen((size_t)np);
+  std::vector<int> lastb((size_t)np, -1);
+  for (int q = 0; q < np; ++q) seen[q].assign((size_t)(paired ? nbands[q] : ntk[q]), 0);
+  for (int64_t t = 0; t < std::min(got, want); ++t) {
+    const int q = tk[t].x, b = tk[t].y & ~nwk::kColTaskPair;
+    const bool flag = (tk[t].y & nwk::kColTaskPair) != 0;
+    CHECK(q >= 0 && q < np, "order %d: pair %d out of range", order, q);
+    if (q < 0 || q >= np) continue;
+    const int span = flag ? 2 : 1;
+    CHECK(b >= 0 && b + span <= (int)seen[q].size(), "order %d: pair %d band %d out of range", order, q, b);
+    if (b < 0 || b + span > (int)seen[q].size()) continue;
+    for (int s = 0; s < span; ++s) seen[q][b + s] += 1;
+    CHECK(b > lastb[q], "order %d: pair %d band %d after band %d", order, q, b, lastb[q]);
+    lastb[q] = b;
+    if (paired) CHECK(b % 2 == 0 && flag == (2 * (b / 2) + 1 < nbands[q]), "order %d: pair %d band %d pair flag %d", order, q, b, (int)flag);
+    else CHECK(!flag, "order %d: pair flag on an unpaired list", order);
+  }
+  for (int q = 0; q < np; ++q)
+    for (size_t b = 0; b < seen[q].size(); ++b)
+      CHECK(seen[q][b] == 1, "order %d paired %d: pair %d band %zu covered %d times", order, (int)paired, q, b, seen[q][b]);
+}
+
+static void check_literal_list(int order, bool paired, const std::vector<std::pair<int, int>>& want) {
+  const int nbands[3] = {3, 1, 2};
+  int ntk[3];
+  for (int q = 0; q < 3; ++q) ntk[q] = paired ? (nbands[q] + 1) / 2 : nbands[q];
+  std::vector<int2> tk(16, make_int2(-1, -1));
+  const int64_t got = nwk::order_tasks(nbands, ntk, 3, order, paired, tk.data());
+  CHECK(got == (int64_t)want.size(), "literal list, order %d: %lld entries", order, (long long)got);
+  for (size_t t = 0; t < want.size(); ++t)
+    CHECK(tk[t].x == want[t].first && tk[t].y == want[t].second, "literal list, order %d paired %d, entry %zu: (%d, %#x)",
+          order, (int)paired, t, tk[t].x, tk[t].y);
+}
+
+static void check_order_tasks() {
+  static const int counts[] = {1, 2, 3, 5};
+  for (int np : {1, 3, 5}) {
+    int64_t combos = 1;
+    for (int q = 0; q < np; ++q) combos *= 4;
+    for (int64_t v = 0; v < combos; ++v) {  // every choice of band counts
+      std::vector<int> nbands((size_t)np);
+      int64_t r = v;
+      for (int q = 0; q < np; ++q, r /= 4) nbands[q] = counts[r % 4];
+      for (int order : {0, 1, 2, 7}) {
+        check_task_list(nbands, order, false, false);
+        check_task_list(nbands, order, false, true);
+        check_task_list(nbands, order, true, false);
+      }
+    }
+  }
+  const int P = nwk::kColTaskPair;
+  check_literal_list(0, false, {{0, 0}, {0, 1}, {0, 2}, {1, 0}, {2, 0}, {2, 1}});
+  check_literal_list(1, false, {{0, 0}, {1, 0}, {2, 0}, {0, 1}, {2, 1}, {0, 2}});
+  check_literal_list(2, false, {{0, 0}, {1, 0}, {0, 1}, {0, 2}, {2, 0}, {2, 1}});
+  check_literal_list(0, true, {{0, 0 | P}, {0, 2}, {1, 0}, {2, 0 | P}});
+}
+
+// form_batch (nwk_sched.h) against the bytes-needed formula written out here
+static void check_form_batch() {
+  const nwk::Footprint fp[3] = {{1000, 50, 160, 0, 0}, {700, 30, 96, 64, 128}, {900, 40, 128, 32, 0}};
+  auto need = [&](size_t n) {  // of the first n pairs: 4 mat + 8 bnd + 3 ops + segops + segctl + 8192
+    int64_t mat = 0, bnd = 0, ops = 0, so = 0, sc = 0;
+    for (size_t q = 0; q < n; ++q) mat += fp[q].mat_dw, bnd += fp[q].bnd_gr, ops += fp[q].ops_b, so += fp[q].segops_b, sc += fp[q].segctl_b;
+    return 4 * mat + 8 * bnd + 3 * ops + so + sc + 8192;
+  };
+  CHECK(fp[1].need() == 4 * 700 + 8 * 30 + 3 * 96 + 64 + 128 + 8192, "Footprint::need");
+  nwk::BatchCut b = nwk::form_batch(fp, 0, 3, need(3) - 1, false);
+  CHECK(b.end == 2 && !b.linear, "budget for two of three: end %zu linear %d", b.end, (int)b.linear);
+  CHECK(b.sum.need() == need(2) && b.sum.mat_dw == 1700 && b.sum.segctl_b == 128, "sums of the first two");
+  b = nwk::form_batch(fp, 0, 3, need(2), false);
+  CHECK(b.end == 2 && !b.linear, "budget equal to the need of two admits two: end %zu", b.end);
+  b = nwk::form_batch(fp, 0, 3, need(3), false);
+  CHECK(b.end == 3 && !b.linear && b.sum.need() == need(3), "budget equal to the need of all admits all: end %zu", b.end);
+  b = nwk::form_batch(fp, 2, 3, need(3), false);
+  CHECK(b.end == 3 && !b.linear && b.sum.need() == fp[2].need(), "a batch from the last pair on");
+  b = nwk::form_batch(fp, 0, 3, need(1) - 1, false);
+  CHECK(b.end == 0 && b.linear && b.need == need(1) && b.sum.need() == 8192, "first pair over the budget: linear, nothing consumed");
+  for (size_t pos = 0; pos < 3; ++pos) {  // forced: every pair is cut off alone for the linear-space path
+    b = nwk::form_batch(fp, pos, 3, need(3) * 4, true);
+    CHECK(b.end == pos && b.linear && b.need == fp[pos].need(), "forced linear at %zu: end %zu linear %d", pos, b.end, (int)b.linear);
+  }
+}
+
 int main() {
+  check_order_tasks();
+  check_form_batch();
   std::string line;
   int n = 0;
   while (std::getline(std::cin, line)) {
